@@ -1,7 +1,19 @@
 """bench.py -- SGC propagation hot path on MI355X: propagated edges/s.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--shape reddit]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: it generates the
+seeded inputs, makes the first call (ingest + plan), runs W warm-up steps,
+times exactly K steps and prints one JSON line (`value`, `ms_per_step` = the
+timed region / K).  --dump-outputs DIR then also writes the X_K the last
+timed step returned to DIR/X_K.npy (float32; above 32 MiB a seeded sample of
+whole rows, the same rows for the same arguments), so two builds can be
+compared output for output.  Everything else described below -- the output
+hash, the instrumented second run and its roofline, the CPU baseline, the
+classifier, the other shapes, the sharded-output propagator at N > 1 -- runs
+only with --full.
 
 `bench.py --gpus N` (N > 1) without torchrun's environment launches its own N
 ranks (a torch.distributed.run child, started before anything touches the
@@ -18,8 +30,9 @@ group (sgc_amd.multigpu: every rank gets the whole X_K, as the reference
 returns it; partition SGC_AMD_PARTITION, default "auto": the first call times
 replicate / features / lines on the node, max over ranks, and keeps the
 fastest -- `config.partition` names it, `config.auto_seconds` lists the
-times); total work fixed, so scaling is "strong".  Beside it (`sharded_output`) the
-partitioned propagator with sharded output (sgc_amd.distributed):
+times); total work fixed, so scaling is "strong".  Beside it, with --full
+(`sharded_output`), the partitioned propagator with sharded output
+(sgc_amd.distributed):
   --partition rows  S row-partitioned (nnz-balanced row blocks, SURVEY.md
                 8(e)); RCCL all-gather of X_k after each hop that feeds another,
                 optionally pipelined in feature groups, hub rows on their own streams
@@ -34,7 +47,7 @@ partitioned propagator with sharded output (sgc_amd.distributed):
   --partition auto (default)  rows vs cyclic vs features (vs tiles), timed
                 on the node (max over ranks); the fastest is kept
 
-Also printed (same JSON line, N = 1):
+Also printed with --full (same JSON line, N = 1):
   roofline      the SpMM hop (spmm_rows_kernel / spmm_csr_kernel, joined with
                 spmm_hub_kernel on its side stream), timed with the library's
                 HIP events on the launch stream (sgc_timing_*, each kernel also
@@ -81,6 +94,8 @@ from sgc_amd.propagate import DeviceCSR, collect_launch_timing, kernel_timing  #
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 BASELINE_METRIC = ("propagated edges/sec (K-hop SpMM) + precompute wall-time, "
                    "Reddit K=2 at 1/2/4/8 GPUs")
+DUMP_BYTES = 32 << 20  # --dump-outputs: array bytes written in all, at the most
+DUMP_SAMPLE_SEED = 20
 SUB_STEPS = {"cora": (20, 5), "pubmed": (20, 5), "reddit": (10, 3), "rmat": (3, 1)}
 
 
@@ -111,6 +126,35 @@ def output_check(shape, K, Y, seed):
     if not rec["output_sha_ok"]:
         rec["output_sha"] = got
     return rec
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write what the last timed step returned, {name: tensor}
+    as <dirname>/<name>.npy (float32, or float64 where the path computes in
+    it), DUMP_BYTES in all at the most.  A larger array is cut to a sample of
+    whole rows: ascending row ids drawn without replacement by PCG64 seed
+    DUMP_SAMPLE_SEED, a function of the array's shape alone, so two builds
+    given the same arguments dump the same rows.  Returns what was written."""
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_BYTES // max(1, len(arrays))
+    written = {}
+    for name, Y in arrays.items():
+        Y = Y.detach()
+        if Y.dtype not in (torch.float32, torch.float64):
+            Y = Y.to(torch.float32)
+        n_rows = Y.shape[0]
+        row_bytes = max(1, Y[0].numel() * Y.element_size())
+        keep = n_rows
+        if n_rows * row_bytes > budget:
+            keep = max(1, budget // row_bytes)
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(
+                n_rows, size=keep, replace=False))
+            Y = Y.index_select(0, torch.from_numpy(rows).to(Y.device))
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(Y.cpu().numpy()))
+        written[name] = {"shape": list(Y.shape), "dtype": str(Y.dtype).replace("torch.", ""),
+                         "rows": "all" if keep == n_rows else
+                         f"{keep} of {n_rows}, seeded sample (seed {DUMP_SAMPLE_SEED})"}
+    return written
 
 
 def gather_model_bytes(n, nnz, F):
@@ -347,12 +391,15 @@ def timed(step, steps, warmup, distributed, dev, on_start=None, on_stop=None, ev
     return elapsed, step_ms, extra
 
 
-def single_gpu_shape(shape, args, dev, lib_sha, steps, warmup, S=None, X_host=None, K=None):
+def single_gpu_shape(shape, args, dev, lib_sha, steps, warmup, S=None, X_host=None, K=None,
+                     full=True, dump_dir=None):
     """One BASELINE config on one GPU through the public call itself --
     sgc_precompute(features, adj, K), reference utils.py:92-97, on a torch COO
     adjacency whose CSR it caches on the first call (as reddit.py's repeated
-    calls would) -- throughput, per-kernel times, roofline and the first-call
-    (ingest + plan + propagation) time."""
+    calls would) -- throughput and the first-call (ingest + plan +
+    propagation) time; with `full`, also the output hash against the golden
+    and a second, instrumented run of the steps for the per-kernel times and
+    the roofline.  `dump_dir`: the last timed call's X_K goes there."""
     import importlib
     prop_mod = importlib.import_module("sgc_amd.propagate")
     from sgc_amd.utils import sgc_precompute
@@ -383,43 +430,47 @@ def single_gpu_shape(shape, args, dev, lib_sha, steps, warmup, S=None, X_host=No
     _, first_s = sgc_precompute(X0, adj, K)
     ingest_s = adj._sgc_amd_csr[1].ingest_seconds
     groups = prop_mod.column_groups_for(adj._sgc_amd_csr[1], F)
-    launches = LaunchTimer(groups)
 
     last = [None]
 
     def step():  # the public call, as the reference's drivers make it
         last[0] = sgc_precompute(X0, adj, K)[0]
 
-    # value: the call as a caller sees it, nothing else in the loop; then the
-    # same number of steps again with the library's per-launch events on (the
-    # roofline's kernel times) -- at Cora shape those events alone would add
-    # more host time per step than the two hops take on the GPU
+    # value: the call as a caller sees it, nothing else in the loop
     elapsed, _, _ = timed(step, steps, warmup, False, dev, events=False)
-    check = output_check(shape, K, last[0], args.seed)  # the last timed call's X_K
-    last[0] = None
-    elapsed_i, step_ms, (hop_ms, light, hub, kernel) = timed(
-        step, steps, 1, False, dev, on_start=launches.start, on_stop=launches.stop)
-    hop_mean = float(np.mean(hop_ms))
     rec = {"value": K * nnz * steps / elapsed, "unit": "edges/s",
            "ms_per_step": elapsed * 1e3 / steps,
-           "ms_per_step_median": float(np.median(step_ms)),
-           "ms_per_step_median_basis": "per-step events of the instrumented run",
-           "ms_per_step_events": [round(v, 4) for v in step_ms],
-           "ms_per_step_instrumented": elapsed_i * 1e3 / steps,
            "steps": steps, "warmup": warmup,
            "config": {"workload": f"{shape}-shape sgc_precompute K={K}", "nodes": n,
                       "undirected_edges": spec["edges"], "nnz": nnz, "features": F, "hops": K},
            "first_call_seconds": round(first_s, 4), "ingest_seconds": round(ingest_s, 4),
            "loader_warmup_seconds": round(warm_s, 4),
            "generate_seconds": round(t_gen, 2),
-           "roofline": roofline(shape, n, nnz, F, hop_mean, mean_or_none(light),
-                                mean_or_none(hub), lib_sha,
-                                f"one hop over all {n} rows" + (
-                                    f" = {groups} column-group dispatches" if groups > 1 else ""),
-                                kernel, groups, mean_or_none(launches.dispatch_light)),
-           "hop_ms_median": float(np.median(hop_ms)),
            "timed_call": "sgc_precompute(features, adj, K) (sgc_amd.utils, the drop-in)"}
-    rec.update(check)
+    if dump_dir:
+        rec["dumped_outputs"] = dump_outputs(dump_dir, {"X_K": last[0]})
+    if full:
+        rec.update(output_check(shape, K, last[0], args.seed))  # the last timed call's X_K
+        last[0] = None
+        # the same number of steps again with the library's per-launch events
+        # on (the roofline's kernel times) -- at Cora shape those events alone
+        # would add more host time per step than the two hops take on the GPU
+        launches = LaunchTimer(groups)
+        elapsed_i, step_ms, (hop_ms, light, hub, kernel) = timed(
+            step, steps, 1, False, dev, on_start=launches.start, on_stop=launches.stop)
+        hop_mean = float(np.mean(hop_ms))
+        rec.update({
+            "ms_per_step_median": float(np.median(step_ms)),
+            "ms_per_step_median_basis": "per-step events of the instrumented run",
+            "ms_per_step_events": [round(v, 4) for v in step_ms],
+            "ms_per_step_instrumented": elapsed_i * 1e3 / steps,
+            "roofline": roofline(shape, n, nnz, F, hop_mean, mean_or_none(light),
+                                 mean_or_none(hub), lib_sha,
+                                 f"one hop over all {n} rows" + (
+                                     f" = {groups} column-group dispatches" if groups > 1 else ""),
+                                 kernel, groups, mean_or_none(launches.dispatch_light)),
+            "hop_ms_median": float(np.median(hop_ms))})
+    last[0] = None
     del X0, adj
     torch.cuda.empty_cache()
     return rec, S, X_host
@@ -611,11 +662,22 @@ def main():
     ap.add_argument("--shape", default="reddit", choices=sorted(graphs.SHAPES))
     ap.add_argument("--hops", type=int, default=None)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the output hash against the golden, the "
+                         "instrumented second run (per-kernel times, roofline), and at N=1 the "
+                         "CPU baseline, the classifier and the other shapes; at N>1 the "
+                         "sharded-output propagator.  Without it: set up, warm up, time "
+                         "--steps steps, print")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's X_K to DIR/X_K.npy (float32; a seeded "
+                         "sample of rows when it is larger than 32 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full, N=1: skip the CPU baseline")
     ap.add_argument("--no-classifier", action="store_true",
-                    help="N=1: skip the classifier sub-record (forward / backward / closure / LBFGS)")
+                    help="--full, N=1: skip the classifier sub-record (forward / backward / "
+                         "closure / LBFGS)")
     ap.add_argument("--shapes", default="cora,pubmed,rmat",
-                    help="N=1: other BASELINE configs measured into the same line "
+                    help="--full, N=1: other BASELINE configs measured into the same line "
                          "(comma list, or 'none')")
     ap.add_argument("--threshold", type=int, default=None, help="heavy-row threshold")
     ap.add_argument("--hub-threshold", type=int, default=None, help="hub-row threshold")
@@ -647,7 +709,7 @@ def main():
     ap.add_argument("--chunks", type=int, default=4,
                     help="N>1 features, replicated output: row chunks of the last hop")
     ap.add_argument("--sharded-steps", type=int, default=5,
-                    help="N>1: steps timed beside the public call with the partitioned "
+                    help="--full, N>1: steps timed beside the public call with the partitioned "
                          "propagator and sharded output (0 = skip)")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="schedule knob for sgc_set_tuning (results never depend on it)")
@@ -696,7 +758,8 @@ def main():
 
     if not distributed:
         main_rec, S, X_host = single_gpu_shape(args.shape, args, dev, lib_sha, args.steps,
-                                               args.warmup, K=K)
+                                               args.warmup, K=K, full=args.full,
+                                               dump_dir=args.dump_outputs)
         cfg = main_rec.pop("config")
         cfg.update({"parallelism": "single-gpu", "heavy_threshold": args.threshold,
                     "hub_threshold": args.hub_threshold})
@@ -706,6 +769,9 @@ def main():
         rec.update(main_rec)
         rec["precompute_seconds"] = rec["ms_per_step"] / 1e3
         rec["lib_sha256"] = lib_sha
+        if not args.full:  # the headline figure alone
+            print(json.dumps(rec), flush=True)
+            return
         if not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(S, X_host)
         del S, X_host
@@ -753,24 +819,30 @@ def main():
     def public_step():
         last[0] = sgc_precompute(X0, adj, K)[0]
     elapsed, _, _ = timed(public_step, args.steps, args.warmup, True, dev, events=False)
-    # every rank's X_K of the last timed call against the reference's hash
-    check = output_check(args.shape, K, last[0], args.seed)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # every rank holds the whole X_K
+        dumped = dump_outputs(args.dump_outputs, {"X_K": last[0]})
+    check, span, hub, kernel = {}, None, None, None
+    if args.full:
+        # every rank's X_K of the last timed call against the reference's hash
+        check = output_check(args.shape, K, last[0], args.seed)
+        last[0] = None
+        okv = torch.tensor([-1 if check["output_sha_ok"] is None else int(check["output_sha_ok"])],
+                           dtype=torch.int32, device=dev if args.dist_backend == "nccl" else "cpu")
+        dist.all_reduce(okv, op=dist.ReduceOp.MIN)
+        check["output_sha_ok_all_ranks"] = None if int(okv.item()) < 0 else bool(okv.item())
+        # the same steps again with the library's per-launch events (rank 0's
+        # launches: the roofline's kernel and times; label from the library)
+        elapsed_i, step_ms, extra = timed(public_step, args.steps, 1, True, dev,
+                                          on_start=launches.start if rank == 0 else None,
+                                          on_stop=launches.stop if rank == 0 else None)
+        span, light, hub, kernel = extra if extra else (None, None, None, None)
     last[0] = None
-    okv = torch.tensor([-1 if check["output_sha_ok"] is None else int(check["output_sha_ok"])],
-                       dtype=torch.int32, device=dev if args.dist_backend == "nccl" else "cpu")
-    dist.all_reduce(okv, op=dist.ReduceOp.MIN)
-    check["output_sha_ok_all_ranks"] = None if int(okv.item()) < 0 else bool(okv.item())
-    # the same steps again with the library's per-launch events (rank 0's
-    # launches: the roofline's kernel and times; label from the library)
-    elapsed_i, step_ms, extra = timed(public_step, args.steps, 1, True, dev,
-                                      on_start=launches.start if rank == 0 else None,
-                                      on_stop=launches.stop if rank == 0 else None)
-    span, light, hub, kernel = extra if extra else (None, None, None, None)
     auto_rec = multigpu.auto_choice(adj._sgc_amd_csr[1], dist.group.WORLD, F, K)
     if partition == "auto" and auto_rec is not None:
         partition = auto_rec["chosen"]
     sharded = None
-    if args.sharded_steps > 0:
+    if args.full and args.sharded_steps > 0:
         # beside it: the partitioned propagator with SHARDED output (each rank
         # keeps its row block of X_K, as a data-parallel classifier would
         # consume it), partition timed on the node (--partition auto)
@@ -807,8 +879,6 @@ def main():
                f"output replicated (every rank gets all of X_K, as the reference returns it)")
         rec.update({"value": K * nnz * args.steps / elapsed,
                     "ms_per_step": elapsed * 1e3 / args.steps,
-                    "ms_per_step_median_rank0": float(np.median(step_ms)),
-                    "ms_per_step_instrumented": elapsed_i * 1e3 / args.steps,
                     "config": {"workload": f"{args.shape}-shape sgc_precompute K={K}", "nodes": n,
                                "undirected_edges": spec["edges"], "nnz": nnz, "features": F,
                                "hops": K, "parallelism": par, "output": "replicated",
@@ -819,6 +889,11 @@ def main():
                     "first_call_seconds": round(first_pub, 4),
                     "loader_warmup_seconds": round(warm_s, 4),
                     "lib_sha256": lib_sha})
+        if dumped is not None:
+            rec["dumped_outputs"] = dumped
+        if args.full:
+            rec.update({"ms_per_step_median_rank0": float(np.median(step_ms)),
+                        "ms_per_step_instrumented": elapsed_i * 1e3 / args.steps})
         rec.update(check)
         if span:
             # rank 0's SpMM launches over one step: the compulsory bytes of its

@@ -30,7 +30,7 @@ for s in $STEPS; do
     p8)     run p8 timeout -k 10 600 python scripts/p8_rehearsal.py ${P8_ARGS} ;;
     rankwork) run rankwork timeout -k 10 400 python scripts/rank_work.py ;;
     smoke)  run smoke timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)  run bench timeout -k 10 600 python bench.py ${BENCH_ARGS} ;;
+    bench)  run bench timeout -k 10 600 python bench.py --full ${BENCH_ARGS} ;;
     aux)    run aux timeout -k 10 600 python scripts/bench_aux.py ;;
     hostov) run hostov timeout -k 10 300 python scripts/host_overhead.py ;;
     ab2)    run ab2 timeout -k 10 400 python scripts/ab_tune.py ${AB2_ARGS} ;;
@@ -38,13 +38,13 @@ for s in $STEPS; do
     ab)     run ab timeout -k 10 400 python scripts/ab_tune.py ${AB_ARGS} ;;
     ab8)    run ab8 timeout -k 10 300 python scripts/ab_tune.py --widths F --rows 8:0 ${AB8_ARGS:-$AB_ARGS} ;;
     locality) run locality timeout -k 10 400 python scripts/locality_ab.py ${LOCALITY_ARGS} ;;
-    selfl)  run selfl timeout -k 10 400 python bench.py --gpus 2 --dist-backend gloo --steps 3 \
+    selfl)  run selfl timeout -k 10 400 python bench.py --full --gpus 2 --dist-backend gloo --steps 3 \
                 --warmup 1 --no-cpu-baseline ${DIST_ARGS} ;;
     rccl1)  run rccl1 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-                --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 1 --steps 5 --warmup 2 \
+                --master-addr 127.0.0.1 --master-port 29534 bench.py --full --gpus 1 --steps 5 --warmup 2 \
                 --distributed-path --no-cpu-baseline ${DIST_ARGS} ;;
     dist)   run dist timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-                --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 3 --warmup 1 \
+                --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 3 --warmup 1 \
                 --dist-backend gloo ${DIST_ARGS} ;;
     dcheck) # 8 ranks on the one GPU (gloo, host-staged exchange): bit-exact X_K at full size
             IFS=, read -ra VARIANTS <<< "${DCHECK_VARIANTS:---partition rows,--partition rows --row-chunks 4,--partition rows --group-floats 256,--partition tiles --col-blocks 2,--partition tiles --col-blocks 4}"
@@ -62,7 +62,7 @@ for s in $STEPS; do
             done ;;
     prof)   cd /tmp && export TMPDIR=/tmp && \
             run prof timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run \
-                --output-format csv -- python3 "$ROOTDIR/bench.py" --steps 10 --warmup 3 --no-cpu-baseline \
+                --output-format csv -- python3 "$ROOTDIR/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline \
                 --shapes none ${BENCH_ARGS}
             cd "$ROOTDIR" ;;
   esac

@@ -9,6 +9,6 @@ for v in ${VARIANTS:-pre3 pre4 pre8 nochain noload}; do
 done
 for v in ${BENCH_VARIANTS:-pre3 pre4 pre8}; do
   echo "== $v" >> $OUT/hub_variants_bench.log
-  SGC_AMD_LIB=variants/$v.so timeout -k 10 180 python bench.py --no-cpu-baseline --steps 20 \
+  SGC_AMD_LIB=variants/$v.so timeout -k 10 180 python bench.py --full --no-cpu-baseline --steps 20 \
     >> $OUT/hub_variants_bench.log 2>&1 || exit $?
 done

@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
 mkdir -p gpurun_out
 for sh in ${SHAPES:-pubmed cora reddit}; do
-  timeout -k 10 300 python bench.py --shape "$sh" --shapes none --no-cpu-baseline \
+  timeout -k 10 300 python bench.py --full --shape "$sh" --shapes none --no-cpu-baseline \
       --steps "${STEPS_N:-30}" --warmup 5 ${ARGS} > gpurun_out/b_$sh.log 2>&1 || exit $?
   python - "$sh" "${ARGS}" >> gpurun_out/shapes.log <<'PY'
 import json, sys

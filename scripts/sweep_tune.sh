@@ -11,7 +11,7 @@ for combo in ${COMBOS:--}; do
   if [ "$combo" != "-" ]; then
     for kv in ${combo//,/ }; do args="$args --tune $kv"; done
   fi
-  timeout -k 10 300 python bench.py --steps ${STEPS_N:-10} --warmup 3 --no-cpu-baseline \
+  timeout -k 10 300 python bench.py --full --steps ${STEPS_N:-10} --warmup 3 --no-cpu-baseline \
     --shapes ${SHAPES:-none} ${EXTRA} $args > $OUT/$i.json 2> $OUT/$i.err
   rc=$?
   echo "[$i] $combo rc=$rc"

@@ -21,11 +21,15 @@ def pytest_configure(config):
 def tiny_cases():
     """{case: {rows, cols, vals, n, X, Y0..Y3}} made by tests/golden/gen_golden.py
     from the reference's own sgc_precompute."""
-    z = np.load(os.path.join(GOLDEN, "tiny_cases.npz"))
+    import glob
+    parts = sorted(glob.glob(os.path.join(GOLDEN, "tiny_cases_[0-9][0-9].npz")))
+    assert parts, "tests/golden/tiny_cases_NN.npz missing"
     cases = {}
-    for key in z.files:
-        name, field = key.split("/")
-        cases.setdefault(name, {})[field] = z[key]
+    for part in parts:  # one archive per < 1 MiB of arrays, keys in order
+        with np.load(part) as z:
+            for key in z.files:
+                name, field = key.split("/")
+                cases.setdefault(name, {})[field] = z[key]
     return cases
 
 

@@ -11,8 +11,9 @@ file is read (the Planetoid/tuning files are pickles; this build never loads
 them) -- graphs and features come from sgc_amd.graphs' seeded generators or
 are built inline below.  Outputs:
 
-  tiny_cases.npz      full inputs + outputs of small hand cases (every edge
-                      case the engine must keep bit-exact)
+  tiny_cases_NN.npz   full inputs + outputs of small hand cases (every edge
+                      case the engine must keep bit-exact), in parts of under
+                      1 MiB each
   shapes.json         sha256 of S (torch COO indices/values as the reference
                       builds them), of X and of X_K for Cora/Pubmed/Reddit-shape
                       graphs, plus timing of the reference CPU path
@@ -173,6 +174,28 @@ def shape_case(shape, Ks, seed=0, fseed=1):
     return rec, samples
 
 
+PART_BYTES = 900_000  # every committed file stays under 1 MiB
+
+
+def write_parts(flat, stem="tiny_cases"):
+    """flat {"case/field": array} into <stem>_NN.npz parts of at most
+    PART_BYTES of array data each, keys kept in order (tests/conftest.py's
+    tiny_cases fixture reads every part); parts of an earlier run are removed."""
+    import glob
+    for old in glob.glob(os.path.join(HERE, f"{stem}_[0-9][0-9].npz")):
+        os.remove(old)
+    parts, size = [{}], 0
+    for k, v in flat.items():
+        if parts[-1] and size + v.nbytes > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += v.nbytes
+    for i, part in enumerate(parts):
+        np.savez_compressed(os.path.join(HERE, f"{stem}_{i:02d}.npz"), **part)
+    return len(parts)
+
+
 def main():
     """python gen_golden.py [tiny] [cora] [pubmed] [reddit] [rmat]; no argument =
     tiny + cora + pubmed + reddit.  rmat (4.19 M nodes, 260 M nnz, F=256, K=3)
@@ -184,8 +207,8 @@ def main():
         for name, d in cases.items():
             for k, v in d.items():
                 flat[f"{name}/{k}"] = v
-        np.savez_compressed(os.path.join(HERE, "tiny_cases.npz"), **flat)
-        print(f"tiny cases: {len(cases)}")
+        n_parts = write_parts(flat)
+        print(f"tiny cases: {len(cases)} in {n_parts} files")
     which = [w for w in which if w != "tiny"]
     Ks = {"cora": (1, 2, 3), "pubmed": (1, 2), "reddit": (2,), "rmat": (3,)}
     out_json = os.path.join(HERE, "shapes.json")

@@ -1,11 +1,12 @@
 """Host-side drop-in surface (no GPU): normalisation, format conversion,
 loaders, args, metrics, model construction, and loud failure off-GPU.
 
-Where /root/reference exists (the build container) the reference's own
-modules are imported and compared against directly; on the GPU box those
-comparisons skip and the committed golden hashes (test_oracle.py) carry the
-parity.  Loader tests read only Planetoid-format files this test writes.
+The comparisons are against what the reference's own modules returned for
+the same seeded inputs, stored in tests/golden/dropin_reference.{npz,json}
+by tests/golden/gen_dropin.py (which imports this module's input builders).
+Loader tests read only Planetoid-format files this test writes.
 """
+import json
 import os
 import pickle
 import sys
@@ -15,35 +16,22 @@ import pytest
 import scipy.sparse as sp
 import torch
 
-REF = os.environ.get("SGC_REFERENCE", "/root/reference")
-HAVE_REF = os.path.isdir(REF) and os.path.exists(os.path.join(REF, "utils.py"))
-needs_ref = pytest.mark.skipif(not HAVE_REF, reason="reference tree not present")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+ADJ_KINDS = ["binary_sym", "weighted", "selfloops", "coo_unsorted", "empty"]
+CITATION_NAMES = ["cora", "citeseer"]
+CITATION_FIELDS = ["features", "labels", "idx_train", "idx_val", "idx_test"]
+ARGV_CASES = [["citation.py"],
+              ["citation.py", "--dataset", "citeseer", "--tuned", "--degree", "3"]]
 
 
 @pytest.fixture(scope="module")
 def ref():
-    """The reference's normalization/utils/metrics/args modules, imported
-    under private names so they cannot shadow anything."""
-    import importlib.util
-    mods = {}
-    sys.path.insert(0, REF)  # reference utils does `from normalization import ...`
-    saved = {k: sys.modules.get(k) for k in ("normalization", "utils", "metrics", "args")}
-    try:
-        for name in ("normalization", "utils", "metrics", "args"):
-            spec = importlib.util.spec_from_file_location(name, os.path.join(REF, f"{name}.py"))
-            m = importlib.util.module_from_spec(spec)
-            sys.modules[name] = m
-            sys.dont_write_bytecode = True
-            spec.loader.exec_module(m)
-            mods[name] = m
-    finally:
-        sys.path.remove(REF)
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
-    return mods
+    """(arrays, meta): the reference's outputs, tests/golden/gen_dropin.py."""
+    with np.load(os.path.join(GOLDEN, "dropin_reference.npz")) as z:
+        arrays = {k: z[k] for k in z.files}
+    with open(os.path.join(GOLDEN, "dropin_reference.json")) as f:
+        meta = json.load(f)
+    return arrays, meta
 
 
 def _rand_adj(rng, n, m, weighted=False, selfloops=False):
@@ -55,10 +43,7 @@ def _rand_adj(rng, n, m, weighted=False, selfloops=False):
     return sp.coo_matrix((v, (r, c)), shape=(n, n))
 
 
-@needs_ref
-@pytest.mark.parametrize("kind", ["binary_sym", "weighted", "selfloops", "coo_unsorted", "empty"])
-def test_aug_normalized_adjacency_matches_reference(ref, kind):
-    from sgc_amd.normalization import aug_normalized_adjacency
+def _adj_case(kind):
     rng = np.random.default_rng(5)
     n = 300
     if kind == "binary_sym":
@@ -74,40 +59,48 @@ def test_aug_normalized_adjacency_matches_reference(ref, kind):
         A = _rand_adj(rng, n, 2000)  # raw COO with duplicates, unsorted
     else:
         A = sp.csr_matrix((n, n))
-    got = aug_normalized_adjacency(A)
-    want = ref["normalization"].aug_normalized_adjacency(A)
-    assert np.array_equal(got.row, want.row) and np.array_equal(got.col, want.col)
-    assert np.array_equal(got.data.view(np.uint64), want.data.view(np.uint64))
+    return A
 
 
-@needs_ref
+@pytest.mark.parametrize("kind", ADJ_KINDS)
+def test_aug_normalized_adjacency_matches_reference(ref, kind):
+    from sgc_amd.normalization import aug_normalized_adjacency
+    arrays, meta = ref
+    got = aug_normalized_adjacency(_adj_case(kind))
+    row, col, data = (arrays[f"augnorm/{kind}/{k}"] for k in ("row", "col", "data"))
+    assert got.getformat() == meta[f"augnorm/{kind}/format"]
+    assert np.array_equal(got.row, row) and np.array_equal(got.col, col)
+    assert got.data.dtype == data.dtype == np.float64
+    assert np.array_equal(got.data.view(np.uint64), data.view(np.uint64))
+
+
 def test_row_normalize_and_fetch(ref):
     from sgc_amd.normalization import fetch_normalization, row_normalize
-    rng = np.random.default_rng(2)
-    X = sp.random(50, 30, density=0.2, random_state=3, format="lil")
-    X[3, :] = 0
+    arrays, meta = ref
+    X = sp.lil_matrix(arrays["row_normalize/X"])  # 20 %-dense, row 3 all zero
+    assert not X[3].toarray().any()
     a = row_normalize(X).toarray()
-    b = ref["normalization"].row_normalize(X).toarray()
-    assert np.array_equal(a, b)
-    bad_mine, bad_ref = fetch_normalization("NormLap"), ref["normalization"].fetch_normalization("NormLap")
+    assert np.array_equal(a, arrays["row_normalize/out"])
+    bad_mine = fetch_normalization("NormLap")
+    assert meta["fetch_NormLap_call_raises"] == "TypeError"  # the reference's own failure
     with pytest.raises(TypeError):
         bad_mine(sp.eye(3))
-    with pytest.raises(TypeError):
-        bad_ref(sp.eye(3))
-    del rng
 
 
-@needs_ref
-def test_sparse_mx_to_torch_matches_reference(ref):
+def _to_torch_case():
     from sgc_amd.normalization import aug_normalized_adjacency
+    return aug_normalized_adjacency(_rand_adj(np.random.default_rng(9), 100, 500))
+
+
+def test_sparse_mx_to_torch_matches_reference(ref):
     from sgc_amd.utils import sparse_mx_to_torch_sparse_tensor
-    rng = np.random.default_rng(9)
-    S = aug_normalized_adjacency(_rand_adj(rng, 100, 500))
-    a = sparse_mx_to_torch_sparse_tensor(S)
-    b = ref["utils"].sparse_mx_to_torch_sparse_tensor(S)
-    assert torch.equal(a._indices(), b._indices())
-    assert torch.equal(a._values(), b._values())
-    assert a.shape == b.shape and a.dtype == b.dtype and not a.is_coalesced()
+    arrays, meta = ref
+    a = sparse_mx_to_torch_sparse_tensor(_to_torch_case())
+    assert torch.equal(a._indices(), torch.from_numpy(arrays["to_torch/indices"]))
+    assert torch.equal(a._values(), torch.from_numpy(arrays["to_torch/values"]))
+    b = meta["to_torch"]
+    assert list(a.shape) == b["shape"] and str(a.dtype) == b["dtype"]
+    assert not b["is_coalesced"] and not a.is_coalesced()
 
 
 def _write_planetoid(root, name, rng, n_train=20, n_val_extra=520, n_test=100, F=40, C=4,
@@ -139,18 +132,24 @@ def _write_planetoid(root, name, rng, n_train=20, n_val_extra=520, n_test=100, F
         f.write("\n".join(str(int(i)) for i in test_idx))
 
 
-@needs_ref
-@pytest.mark.parametrize("name", ["cora", "citeseer"])
+def _write_citation_case(root, name):
+    _write_planetoid(root, name, np.random.default_rng(1), isolated=(name == "citeseer"))
+
+
+@pytest.mark.parametrize("name", CITATION_NAMES)
 def test_load_citation_matches_reference(ref, tmp_path, monkeypatch, name):
     from sgc_amd.utils import load_citation
-    _write_planetoid(str(tmp_path), name, np.random.default_rng(1), isolated=(name == "citeseer"))
+    arrays, meta = ref
+    _write_citation_case(str(tmp_path), name)
     monkeypatch.chdir(tmp_path)
     a = load_citation(name, "AugNormAdj", cuda=False)
-    b = ref["utils"].load_citation(name, "AugNormAdj", cuda=False)
-    assert torch.equal(a[0]._indices(), b[0]._indices())
-    assert torch.equal(a[0]._values(), b[0]._values())
-    for x, y in zip(a[1:], b[1:]):
-        assert torch.equal(x, y)
+    assert len(a) == 1 + len(CITATION_FIELDS)
+    assert torch.equal(a[0]._indices(), torch.from_numpy(arrays[f"citation/{name}/adj_indices"]))
+    assert torch.equal(a[0]._values(), torch.from_numpy(arrays[f"citation/{name}/adj_values"]))
+    assert list(a[0].shape) == meta[f"citation/{name}/adj_shape"]
+    for x, key in zip(a[1:], CITATION_FIELDS):
+        y = torch.from_numpy(arrays[f"citation/{name}/{key}"])
+        assert x.dtype == y.dtype and torch.equal(x, y), key
 
 
 def test_load_reddit_npz_roundtrip(tmp_path, monkeypatch):
@@ -177,23 +176,28 @@ def test_load_reddit_npz_roundtrip(tmp_path, monkeypatch):
     assert labels.dtype == torch.int64
 
 
-@needs_ref
 def test_args_defaults_match_reference(ref, monkeypatch):
     from sgc_amd.args import get_citation_args
-    monkeypatch.setattr(sys, "argv", ["citation.py"])
-    assert vars(get_citation_args()) == vars(ref["args"].get_citation_args())
-    monkeypatch.setattr(sys, "argv", ["citation.py", "--dataset", "citeseer", "--tuned", "--degree", "3"])
-    assert vars(get_citation_args()) == vars(ref["args"].get_citation_args())
+    recs = ref[1]["args"]
+    assert [r["argv"] for r in recs] == ARGV_CASES
+    for r in recs:
+        monkeypatch.setattr(sys, "argv", list(r["argv"]))
+        want = dict(r["namespace"])
+        # reference args.py:39, the one entry that depends on the host
+        want["cuda"] = not want["no_cuda"] and torch.cuda.is_available()
+        assert vars(get_citation_args()) == want
 
 
-@needs_ref
 def test_metrics_match_reference(ref):
     from sgc_amd.metrics import accuracy, f1
-    g = torch.Generator().manual_seed(0)
-    out = torch.randn(200, 7, generator=g)
-    lab = torch.randint(0, 7, (200,), generator=g)
-    assert torch.equal(accuracy(out, lab), ref["metrics"].accuracy(out, lab))
-    assert f1(out, lab) == ref["metrics"].f1(out, lab)
+    arrays, _ = ref
+    out = torch.from_numpy(arrays["metrics/out"])
+    lab = torch.from_numpy(arrays["metrics/lab"])
+    assert out.shape == (200, 7) and lab.dtype == torch.int64
+    want = torch.from_numpy(arrays["metrics/accuracy"])
+    got = accuracy(out, lab)
+    assert got.dtype == want.dtype and torch.equal(got, want)
+    assert f1(out, lab) == tuple(float(v) for v in arrays["metrics/f1"])
 
 
 def test_model_surface():

@@ -313,7 +313,7 @@ def test_bench_self_launch_two_ranks():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "bench.py", "--gpus", "2", "--dist-backend", "gloo", "--shape",
-           "pubmed", "--steps", "2", "--warmup", "1", "--sharded-steps", "1"]
+           "pubmed", "--steps", "2", "--warmup", "1", "--sharded-steps", "1", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _last_json(r.stdout)
