@@ -70,6 +70,12 @@ const char *sgc_last_error(void);
  *                   the multi-row kernel, 2 in the one-row kernel, 4 four
  *                   nonzeros per load up to 32 floats, 8 the same transposed
  *                   at 33..64 floats, 16 the pairs transposed;
+ *   "x16_vec":      widest per-lane load of the 16-bit-feature launches, 8,
+ *                   4, 2 or 1 elements (feature slices of 64 x that); 0 =
+ *                   default: 8 up to 512 features (one slice), else 4;
+ *   "x16_step":     nonzeros per step of their light rows at 16-B lanes, 8
+ *                   or 4 (two steps in flight); 0 = default: 4 on launches
+ *                   below 65,536 rows, else 8;
  *   "tile_buffers": classifier LDS tile images, 1 (default) or 2;
  *   "linear_kernel": classifier forward, 0 = auto (the streaming kernel where
  *                   W^T fits LDS and M >= 4096), 1 = LDS tile, 2 = streaming
@@ -397,6 +403,45 @@ int sgc_launch_list_destroy(int64_t handle);
 
 /* The row stride (floats) the engine uses for its own feature buffers. */
 int64_t sgc_aligned_ld(int64_t F);
+
+/* One hop with the features stored in 16 bits: 16 bits in memory, fp32
+ * everywhere else.  x_dtype = SGC_DTYPE_BF16 or SGC_DTYPE_F16 (torch.bfloat16
+ * / torch.float16 bit patterns); y_dtype = x_dtype, or SGC_DTYPE_F32; S (val)
+ * stays fp32.  ldx / ldy count elements of X's / Y's own type.  Every output
+ * element is
+ *     Y[i,f] = round_T(chain),  chain: acc = +0.0f; for k in row i, CSR order:
+ *                                          acc = fmaf(val[k], (float)X[col[k],f], acc)
+ * -- the single sequential fp32 FMA chain of sgc_spmm_csr_f32 (never split
+ * across lanes or waves) on the exactly widened elements, rounded to nearest
+ * even once per output element: for finite values the bits of torch's CPU
+ * tensor.to(T), subnormal results and fp16 overflow to +-inf included; NaN
+ * stays NaN (any payload).  With y_dtype = SGC_DTYPE_F32 the unrounded chain
+ * is stored.  So a hop is bit-identical to
+ *     sgc_spmm_csr_f32(S, (float)X) converted to T,
+ * and a K-hop loop through 16-bit buffers to K such hops; the plan (plan,
+ * n_heavy, n_hub, heavy_threshold, as sgc_spmm_csr_f32) is a schedule only.
+ * flags: the bits of sgc_spmm_csr_f32_ex.  For a 16-bit operand the padded
+ * flags mean columns [F, round8(F)) (readable in X / writable in Y);
+ * the 4 GiB flag means n_cols * ldx * 2 < 2^32; the accumulate flag
+ * is accepted only with y_dtype = SGC_DTYPE_F32 (a chain carried through a
+ * 16-bit store would not be exact) -- any other combination, or an unknown
+ * dtype, returns SGC_EINVAL with an sgc_last_error text.
+ * 16-byte lanes (8 elements) need 16-B aligned X rows (the engine's buffers:
+ * rows of sgc_aligned_ld_x16(F) elements); any other even-byte layout -- an
+ * odd ldx, a base that is only 2-B aligned -- runs on narrower loads with the
+ * same bits.  Columns >= F are never stored, and never read unless the caller
+ * set the padded flags. */
+enum { SGC_DTYPE_F32 = 0, SGC_DTYPE_BF16 = 1, SGC_DTYPE_F16 = 2 };
+int sgc_spmm_csr_x16(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
+                     int64_t row_begin, int64_t row_end,
+                     const void *X, int32_t x_dtype, int64_t ldx,
+                     void *Y, int32_t y_dtype, int64_t ldy, int64_t F,
+                     const int32_t *plan, int64_t n_heavy, int64_t n_hub,
+                     int32_t heavy_threshold, uint32_t flags, void *stream);
+
+/* The row stride (16-bit elements) of the engine's own 16-bit feature
+ * buffers: F rounded up to 64 elements (128-B rows). */
+int64_t sgc_aligned_ld_x16(int64_t F);
 
 /* ---------------------------------------------------------------------------
  * Classifier forward Y[M,C] = X[M,K] . W[C,K]^T + b[C]  (models.py:17-18,

@@ -60,6 +60,9 @@ SIGNATURES = {
     "sgc_wait_flags_i32": (ctypes.c_int, [_i32, _p, _i32, _p, _i64, _p]),
     "sgc_pull_blocks_f32": (ctypes.c_int, [_i32, _p, _p, _i64, _p]),
     "sgc_aligned_ld": (_i64, [_i64]),
+    "sgc_spmm_csr_x16": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _p, _i32, _i64, _p, _i32, _i64,
+                                        _i64, _p, _i64, _i64, _i32, _u32, _p]),
+    "sgc_aligned_ld_x16": (_i64, [_i64]),
     "sgc_launch_list_create": (ctypes.c_int, [ctypes.POINTER(_i64)]),
     "sgc_launch_list_add_spmm": (ctypes.c_int, [_i64, _p, _p, _p, _i64, _i64, _p, _i64, _p, _i64,
                                                 _i64, _p, _i64, _i64, _i32, _u32, _i32, _i32]),

@@ -35,6 +35,11 @@ int launch_spmm(const int32_t *row_ptr, const int32_t *col_idx, const float *val
                 int64_t row_begin, int64_t row_end, const float *X, int64_t ldx, float *Y,
                 int64_t ldy, int64_t F, const int32_t *heavy_rows, int64_t n_heavy,
                 int64_t n_hub, int32_t heavy_threshold, uint32_t flags, hipStream_t stream);
+int launch_spmm_x16(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
+                    int64_t row_begin, int64_t row_end, const void *X, int32_t x_dtype,
+                    int64_t ldx, void *Y, int32_t y_dtype, int64_t ldy, int64_t F,
+                    const int32_t *heavy_rows, int64_t n_heavy, int64_t n_hub,
+                    int32_t heavy_threshold, uint32_t flags, hipStream_t stream);
 int launch_pad_rows(const float *src, int64_t lds, float *dst, int64_t ldd, int64_t n_rows,
                     int64_t F, hipStream_t stream);
 int launch_copy_blocks(const float *src, int64_t lds, float *dst, int64_t ldd, int32_t nseg,
@@ -241,7 +246,25 @@ int sgc_spmm_csr_f32_ex(const int32_t *row_ptr, const int32_t *col_idx, const fl
                        as_stream(stream));
 }
 
+int sgc_spmm_csr_x16(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
+                     int64_t row_begin, int64_t row_end, const void *X, int32_t x_dtype,
+                     int64_t ldx, void *Y, int32_t y_dtype, int64_t ldy, int64_t F,
+                     const int32_t *plan, int64_t n_heavy, int64_t n_hub,
+                     int32_t heavy_threshold, uint32_t flags, void *stream) {
+    constexpr uint32_t known = SGC_SPMM_X_PADDED | SGC_SPMM_Y_PADDED | SGC_SPMM_NO_HUB |
+                               SGC_SPMM_HUB_ONLY | SGC_SPMM_ACCUMULATE | SGC_SPMM_HUB_SERIAL |
+                               SGC_SPMM_LIGHT_ORDER | SGC_SPMM_X_UNDER_4G;
+    SGC_REQUIRE((flags & ~known) == 0, SGC_EINVAL, "spmm_x16: unknown flags 0x%x", flags);
+    SGC_REQUIRE(!((flags & SGC_SPMM_NO_HUB) && (flags & SGC_SPMM_HUB_ONLY)), SGC_EINVAL,
+                "spmm_x16: NO_HUB and HUB_ONLY together");
+    return launch_spmm_x16(row_ptr, col_idx, val, row_begin, row_end, X, x_dtype, ldx, Y, y_dtype,
+                           ldy, F, plan, plan ? n_heavy : 0, plan ? n_hub : 0, heavy_threshold,
+                           flags, as_stream(stream));
+}
+
 int64_t sgc_aligned_ld(int64_t F) { return F <= 0 ? 0 : (F + 31) / 32 * 32; }
+
+int64_t sgc_aligned_ld_x16(int64_t F) { return F <= 0 ? 0 : (F + 63) / 64 * 64; }
 
 static bool needs_pad(int64_t ldx, const float *X0) {
     return (ldx % 32) != 0 || (reinterpret_cast<uintptr_t>(X0) % 128) != 0;

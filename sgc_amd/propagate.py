@@ -480,6 +480,158 @@ def csr_of(adj):
     return csr
 
 
+# 16-bit feature storage (sgc_spmm_csr_x16: 16 bits in memory, the fp32 FMA
+# chains in registers, one round-to-nearest-even per stored element).
+X16_DTYPES = {torch.bfloat16: 1, torch.float16: 2}  # -> SGC_DTYPE_* (include/sgc_amd.h)
+
+
+def is_x16(X):
+    return isinstance(X, torch.Tensor) and X.dtype in X16_DTYPES
+
+
+def require_f32_features(X, what):
+    """The paths that only exist for fp32 features refuse 16-bit ones loudly
+    (none of them may run an fp32 kernel over 16-bit memory)."""
+    if is_x16(X):
+        raise TypeError(f"sgc_amd: {what} supports float32 features only, got {X.dtype}: "
+                        "16-bit features run through spmm / propagate / sgc_precompute on "
+                        "one GPU (or the CPU)")
+
+
+def _sgc_dtype(dtype):
+    return 0 if dtype == torch.float32 else X16_DTYPES[dtype]
+
+
+def aligned_ld_x16(F):
+    """Row stride (elements) of the engine's own 16-bit feature buffers: 128-B rows."""
+    return (F + 63) // 64 * 64
+
+
+def _needs_pad_x16(X):
+    return X.stride(0) % 64 != 0 or X.data_ptr() % 128 != 0
+
+
+def x16_flags(X):
+    """SPMM_X_UNDER_4G for a 16-bit X: < 2^24 rows, all within 4 GiB."""
+    n, ld = X.shape[0], X.stride(0)
+    return SPMM_X_UNDER_4G if n < (1 << 24) and n * ld * 2 < (1 << 32) else 0
+
+
+def _out_dtype16(X, out, out_dtype):
+    """The output type of a 16-bit launch: X's, or float32."""
+    want = out.dtype if out is not None and out_dtype is None else out_dtype
+    want = X.dtype if want is None else want
+    if want not in (X.dtype, torch.float32):
+        raise TypeError(f"sgc_amd: {X.dtype} features give {X.dtype} or float32 output, "
+                        f"not {want}")
+    if out is not None and out.dtype != want:
+        raise TypeError(f"sgc_amd: out is {out.dtype}, out_dtype {want}")
+    return want
+
+
+def _spmm_cpu_x16(csr, X, row_begin, row_end, out, flags):
+    """The definition itself on CPU tensors: the host twin on X.float(), then
+    one rounding to the output type (none for float32)."""
+    lib = _lib.load()
+    Xf = X.float().contiguous()
+    F = X.shape[1]
+    if flags & SPMM_HUB_ONLY:
+        return out
+    acc = out if out.dtype == torch.float32 else torch.empty((row_end - row_begin, F),
+                                                             dtype=torch.float32)
+    _lib.check(lib.sgc_spmm_csr_f32_cpu_ex(_lib.ptr(csr.row_ptr), _lib.ptr(csr.col_idx),
+                                           _lib.ptr(csr.val), row_begin, row_end, _lib.ptr(Xf),
+                                           Xf.stride(0), _lib.ptr(acc), acc.stride(0), F,
+                                           int(flags) & SPMM_ACCUMULATE, cpu_threads()),
+               "spmm_csr_f32_cpu")
+    if acc is not out:
+        out.copy_(acc)  # torch's CPU conversion: round to nearest even
+    return out
+
+
+def _spmm_x16(csr, X, row_begin, row_end, out, use_plan, threshold, hub_threshold, flags,
+              out_dtype):
+    F = X.shape[1]
+    want = _out_dtype16(X, out, out_dtype)
+    if flags & SPMM_ACCUMULATE and want != torch.float32:
+        raise TypeError("sgc_amd: SPMM_ACCUMULATE needs a float32 out (a chain carried through "
+                        "a 16-bit store would not be exact)")
+    if out is None:
+        if flags & SPMM_ACCUMULATE:
+            raise ValueError("sgc_amd: SPMM_ACCUMULATE continues the chains in `out`; pass it")
+        out = torch.empty((row_end - row_begin, F), dtype=want, device=X.device)
+    if out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (row_end - row_begin, F):
+        raise RuntimeError("sgc_amd: out must be [rows, F] with unit column stride")
+    if F == 0 or row_end == row_begin:
+        return out
+    if X.device.type == "cpu":
+        return _spmm_cpu_x16(csr, X, row_begin, row_end, out, flags)
+    lib = _lib.load()
+    with torch.cuda.device(X.device):
+        pl = csr.plan(row_begin, row_end, threshold, hub_threshold, F) if use_plan else NO_PLAN
+        _lib.check(lib.sgc_spmm_csr_x16(_lib.ptr(csr.row_ptr), _lib.ptr(csr.col_idx),
+                                        _lib.ptr(csr.val), row_begin, row_end, _lib.ptr(X),
+                                        _sgc_dtype(X.dtype), X.stride(0), _lib.ptr(out),
+                                        _sgc_dtype(out.dtype), out.stride(0), F,
+                                        _lib.ptr(pl.rows), pl.n_heavy, pl.n_hub, pl.threshold,
+                                        int(flags) | pl.hub_flags() | x16_flags(X),
+                                        _lib.stream_handle(X.device)), "spmm_csr_x16")
+    return out
+
+
+def _propagate_x16(csr, X, K, out, use_plan, threshold, hub_threshold, hop_hook, out_dtype):
+    """propagate() for bfloat16 / float16 features: X_{k+1} = fp32_spmm(S,
+    X_k.float()).to(T) bit for bit; the last hop writes X's dtype or, with
+    out_dtype=torch.float32, its unrounded fp32 chains.  One launch per hop:
+    column groups would need ACCUMULATE through an fp32 buffer."""
+    n, F = X.shape
+    want = _out_dtype16(X, out, out_dtype)
+    if out is None:
+        out = torch.empty((n, F), dtype=want, device=X.device)
+    if out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (n, F):
+        raise RuntimeError("sgc_amd: out must be [N, F] with unit column stride")
+    if n == 0 or F == 0:
+        return out
+    if X.device.type == "cpu":
+        src = X
+        for h in range(K):
+            dst = out if h == K - 1 else torch.empty((n, F), dtype=X.dtype)
+            _spmm_cpu_x16(csr, src, 0, n, dst, 0)
+            src = dst
+        return out
+    lib = _lib.load()
+    stream = torch.cuda.current_stream(X.device).cuda_stream
+    pl = csr.plan(0, n, threshold, hub_threshold, F) if use_plan else NO_PLAN
+    ldw = aligned_ld_x16(F)
+    with torch.cuda.device(X.device):
+        # the 2-byte re-layout's copy moves 4 B per element against 64 B per
+        # nonzero saved, the same ratio as pad_pays' fp32 rule
+        pad = _needs_pad_x16(X) and (pad_pays(csr, F) if PAD_X0 is None else bool(PAD_X0))
+        n_bufs = min(2, int(pad) + min(K - 1, 2))
+        bufs = [torch.empty((n, ldw), dtype=X.dtype, device=X.device) for _ in range(n_bufs)]
+        src, nxt = X, 0
+        if pad:
+            bufs[0][:, :F].copy_(X)  # (a torch strided copy)
+            src, nxt = bufs[0][:, :F], 1 % len(bufs)
+        for h in range(K):
+            dst = out if h == K - 1 else bufs[nxt][:, :F]
+            # the engine's own buffers may be read / written in their pad columns
+            flags = ((SPMM_X_PADDED if src is not X else 0) |
+                     (SPMM_Y_PADDED if dst is not out else 0) | x16_flags(src) | pl.hub_flags())
+            if hop_hook:
+                hop_hook("start", h)
+            _lib.check(lib.sgc_spmm_csr_x16(_lib.ptr(csr.row_ptr), _lib.ptr(csr.col_idx),
+                                            _lib.ptr(csr.val), 0, n, _lib.ptr(src),
+                                            _sgc_dtype(src.dtype), src.stride(0), _lib.ptr(dst),
+                                            _sgc_dtype(dst.dtype), dst.stride(0), F,
+                                            _lib.ptr(pl.rows), pl.n_heavy, pl.n_hub,
+                                            pl.threshold, flags, stream), "spmm_csr_x16")
+            if hop_hook:
+                hop_hook("end", h)
+            src, nxt = dst, nxt ^ 1
+    return out
+
+
 def _check_features(X, csr):
     if not isinstance(X, torch.Tensor):
         raise TypeError("sgc_amd: features must be a torch.Tensor")
@@ -487,8 +639,9 @@ def _check_features(X, csr):
         _require_device(X, "features")
     if X.device != csr.device:
         raise RuntimeError(f"sgc_amd: features on {X.device} but adj on {csr.device}")
-    if X.dtype != torch.float32:
-        raise TypeError(f"sgc_amd: features must be float32, got {X.dtype}")
+    if X.dtype != torch.float32 and X.dtype not in X16_DTYPES:
+        raise TypeError(f"sgc_amd: features must be float32, got {X.dtype} "
+                        "(bfloat16 / float16 features: spmm, propagate, sgc_precompute)")
     if X.dim() != 2 or X.shape[0] != csr.n_cols:
         raise RuntimeError(f"sgc_amd: size mismatch, adj {csr.n_rows}x{csr.n_cols} . "
                            f"features {tuple(X.shape)}")
@@ -507,15 +660,23 @@ def check_propagation_inputs(csr: DeviceCSR, X: torch.Tensor):
 
 
 def spmm(csr: DeviceCSR, X: torch.Tensor, row_begin=0, row_end=None, out=None,
-         use_plan=True, threshold=None, hub_threshold=None, flags=0):
+         use_plan=True, threshold=None, hub_threshold=None, flags=0, out_dtype=None):
     """One hop Y = S[row_begin:row_end] . X (bit-exact with torch.spmm on CPU).
     flags: SPMM_* bits of sgc_spmm_csr_f32_ex (a split launch on the GPU: NO_HUB
     / HUB_ONLY; on the CPU the whole hop runs for the NO_HUB part and nothing
     for HUB_ONLY, so the two parts still write every row once; ACCUMULATE
-    continues the FMA chains already in `out`, which must then be given)."""
+    continues the FMA chains already in `out`, which must then be given).
+    bfloat16 / float16 X (sgc_spmm_csr_x16): the same fp32 chains on the
+    widened elements, rounded once into X's dtype -- or stored unrounded with
+    out_dtype=torch.float32 (the only output ACCUMULATE continues)."""
     X = _check_features(X, csr)
     row_end = csr.n_rows if row_end is None else row_end
     F = X.shape[1]
+    if is_x16(X):
+        return _spmm_x16(csr, X, row_begin, row_end, out, use_plan, threshold, hub_threshold,
+                         flags, out_dtype)
+    if out_dtype not in (None, torch.float32):
+        raise TypeError(f"sgc_amd: float32 features give float32 output, not {out_dtype}")
     if out is None:
         if flags & SPMM_ACCUMULATE:
             raise ValueError("sgc_amd: SPMM_ACCUMULATE continues the chains in `out`; pass it")
@@ -566,6 +727,7 @@ class SpmmLaunch:
     def __init__(self, csr: DeviceCSR, X: torch.Tensor, out: torch.Tensor, row_begin=0,
                  row_end=None, flags=0, threshold=None, hub_threshold=None, keep_tensors=True):
         X = _check_features(X, csr)
+        require_f32_features(X, "SpmmLaunch (prepared launches)")
         if X.device.type != "cuda":
             raise RuntimeError("SpmmLaunch: ROCm tensors only")
         row_end = csr.n_rows if row_end is None else row_end
@@ -611,7 +773,7 @@ def pad_pays(csr, F):
 
 
 def propagate(csr: DeviceCSR, X: torch.Tensor, K: int, out=None, use_plan=True, threshold=None,
-              hop_hook=None, native_loop=False, hub_threshold=None, prepare=True):
+              hop_hook=None, native_loop=False, hub_threshold=None, prepare=True, out_dtype=None):
     """X_K = S^K X on the device (K >= 1); asynchronous on the current stream.
 
     Mirrors sgc_propagate_f32: X is first re-laid into 128-B aligned rows when
@@ -622,9 +784,23 @@ def propagate(csr: DeviceCSR, X: torch.Tensor, K: int, out=None, use_plan=True, 
     around each hop's launch ("start"/"end", for event timing).
     native_loop=True runs the same loop inside the C ABI call instead.
     prepare=False neither replays nor records a launch list (GraphedPropagation's
-    warm-up and capture; nothing is kept under a stream capture either)."""
+    warm-up and capture; nothing is kept under a stream capture either).
+    bfloat16 / float16 X: hops ping-pong between two 16-bit buffers (rows of
+    aligned_ld_x16(F) elements), each hop one sgc_spmm_csr_x16 launch, every
+    hop's fp32 chains rounded once into X's dtype; out_dtype=torch.float32
+    makes the last hop store its chains unrounded.  No launch list, native
+    loop or column groups there.  K <= 0 returns X itself."""
     X = check_propagation_inputs(csr, X)
     n, F = X.shape
+    if is_x16(X):
+        if native_loop:
+            require_f32_features(X, "propagate(native_loop=True)")
+        if K <= 0:
+            return X
+        return _propagate_x16(csr, X, K, out, use_plan, threshold, hub_threshold, hop_hook,
+                              out_dtype)
+    if out_dtype not in (None, torch.float32):
+        raise TypeError(f"sgc_amd: float32 features give float32 output, not {out_dtype}")
     if out is None:
         out = torch.empty((n, F), dtype=torch.float32, device=X.device)
     if n == 0 or F == 0 or K <= 0:
@@ -804,6 +980,7 @@ class GraphedPropagation:
 
     def run(self, X: torch.Tensor) -> torch.Tensor:
         X = _check_features(X, self.csr)
+        require_f32_features(X, "GraphedPropagation")
         if tuple(X.shape) != tuple(self.x_in.shape):
             raise RuntimeError(f"GraphedPropagation: captured for {tuple(self.x_in.shape)}, "
                                f"got {tuple(X.shape)}")

@@ -21,7 +21,8 @@ import torch
 
 from . import multigpu
 from .normalization import aug_normalize_on_device, fetch_normalization, row_normalize
-from .propagate import check_propagation_inputs, csr_of, propagate, to_torch_coo, warmup
+from .propagate import (check_propagation_inputs, csr_of, propagate, require_f32_features,
+                        to_torch_coo, warmup)
 
 # under torchrun: this process's `.cuda()` is its own GPU (cuda:LOCAL_RANK),
 # so an unchanged reddit.py / citation.py spreads over the node's GPUs
@@ -89,7 +90,11 @@ def sgc_precompute(features, adj, degree):
     any number of GPUs: under torchrun (or an initialised process group of
     world > 1) the hops run partitioned over the ranks and every rank gets
     the whole X_K; with SGC_AMD_DEVICES one process drives several GPUs
-    (sgc_amd.multigpu)."""
+    (sgc_amd.multigpu).
+    bfloat16 / float16 features (one GPU or the CPU; the adjacency stays
+    float32) return their own dtype: every hop is the fp32 chain on the
+    widened features, rounded once to nearest even, i.e. bit for bit
+    X_{k+1} = spmm(adj, X_k.float()).to(dtype)."""
     if degree <= 0:
         t = perf_counter()
         return features, perf_counter() - t
@@ -121,11 +126,13 @@ def _propagate_on_node(csr, X, K):
     group = multigpu.process_group(X.device)
     if group is not None:
         X = check_propagation_inputs(csr, X)
+        require_f32_features(X, "sgc_precompute under a process group (partitioned hops)")
         return multigpu.precompute_group(csr, X, K, group)
     if X.device.type == "cuda":
         devices = multigpu.devices_from_env(X.device.index)
         if devices:
             X = check_propagation_inputs(csr, X)
+            require_f32_features(X, "sgc_precompute with SGC_AMD_DEVICES")
             return multigpu.precompute_devices(csr, X, K, devices)
     return propagate(csr, X, K)
 
