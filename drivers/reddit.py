@@ -45,6 +45,8 @@ def parse(argv=None):
     p.add_argument("--degree", type=int, default=2, help="degree of the approximation.")
     p.add_argument("--synthetic", type=int, default=0,
                    help="use a seeded Reddit-shape synthetic graph with this many nodes (0: read data/)")
+    p.add_argument("--device-lbfgs", action="store_true", default=False,
+                   help="train with sgc_amd.optim.LBFGS (no host synchronisation per iteration)")
     args = p.parse_args(argv)
     args.cuda = not args.no_cuda and torch.cuda.is_available()
     return args
@@ -78,8 +80,12 @@ def synthetic_reddit(n, seed=0):
     return out
 
 
-def train_regression(model, train_features, train_labels, epochs):
-    optimizer = optim.LBFGS(model.parameters(), lr=1)
+def train_regression(model, train_features, train_labels, epochs, device_lbfgs=False):
+    if device_lbfgs:  # the whole L-BFGS iteration on the GPU (sgc_amd/optim.py)
+        from sgc_amd.optim import LBFGS
+        optimizer = LBFGS(model.parameters(), lr=1)
+    else:
+        optimizer = optim.LBFGS(model.parameters(), lr=1)
     model.train()
 
     def closure():
@@ -117,7 +123,8 @@ def main(argv=None):
     else:
         train_features = processed[idx_train]
     test_features = processed[idx_test if args.test else idx_val]
-    model, train_time = train_regression(model, train_features, labels[idx_train], args.epochs)
+    model, train_time = train_regression(model, train_features, labels[idx_train], args.epochs,
+                                         device_lbfgs=args.device_lbfgs)
     test_f1, _ = test_regression(model, test_features, labels[idx_test if args.test else idx_val])
     print("Total Time: {:.4f}s, {} F1: {:.4f}".format(train_time + precompute_time,
                                                       "Test" if args.test else "Val", test_f1))

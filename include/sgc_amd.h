@@ -519,6 +519,69 @@ int sgc_linear_xent_f32(const float *X, int64_t ldx, const float *W, const float
                         int64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Device-resident L-BFGS: replaces optim.LBFGS(lr=1).step(closure) of
+ * reddit.py:51-64, the form with line_search_fn=None only.  torch's loop
+ * synchronises with the host on every dot product and every termination
+ * test; here the loop is cut at the closure boundary: after each closure one
+ * launch (sgc_lbfgs_iterate_f32, one 1024-thread workgroup) runs the
+ * termination tests of the iteration just taken and then the memory update,
+ * the two-loop recursion, the step size and the in-place parameter update of
+ * the next one.  A device stop word turns every later launch of the step
+ * into a no-op, so the host reads the status once per step.
+ *
+ * Arithmetic: vectors fp32; every dot product, |g|_1, max|g| and max|t d| is
+ * accumulated in fp64 in a fixed order from exact products of the fp32
+ * elements and rounded to fp32 once; elementwise updates are single fmafs.
+ * Bitwise reproducible run to run; tolerance-equal to torch, not bit-equal
+ * (another summation order).  Every comparison takes torch's branch on NaN
+ * (all false: a NaN loss or gradient stops nothing and pushes no pair).
+ *
+ *   sgc_lbfgs_workspace(n, history_size): bytes of the caller-owned device
+ *     state (256-B aligned), 0 with an error text for n outside 1..65536 or
+ *     history_size outside 1..1024.  Layout: a 256-B scalar block, then
+ *     ro[history_size] (padded to 256 B), d[ld], prev_g[ld], S[history_size][ld],
+ *     Y[history_size][ld] with ld = n rounded up to 32 floats (al of the
+ *     two-loop recursion lives in LDS during a launch).  The scalar block
+ *     starts with six int64 -- n_iter and func_evals (global, as torch's
+ *     state), iters and evals (this step), stop (SGC_LBFGS_STOP_*), hist_len
+ *     -- which sgc_lbfgs_read_status copies back; after them the ring head,
+ *     n, history_size, ld (int64), loss and prev_loss (double), H_diag and t
+ *     (float).
+ *   sgc_lbfgs_init: zero the state and record its shape.  Asynchronous.
+ *   sgc_lbfgs_begin_step: reset iters, evals and stop.  Asynchronous.
+ *   sgc_lbfgs_iterate_f32: the launch above, after a closure.  n_tensors
+ *     (1..16) contiguous fp32 parameter tensors of numels_host[i] elements
+ *     (summing to the state's n) at param_ptrs_host[i], their gradients at
+ *     grad_ptrs_host[i] (a NULL entry is a zero gradient, as torch
+ *     substitutes for p.grad is None); the three host tables travel as kernel
+ *     arguments.  loss: the closure's value, one device float.  Asynchronous,
+ *     never synchronises.
+ *   sgc_lbfgs_read_status: out_host[0..6) = n_iter, func_evals, iters, evals,
+ *     stop reason, hist_len.  Synchronous.
+ * Argument errors return SGC_EINVAL / SGC_ERANGE (n > 65536, history_size >
+ * 1024) before any device call.
+ * ------------------------------------------------------------------------- */
+enum {
+    SGC_LBFGS_STOP_NONE = 0,         /* the step is still running               */
+    SGC_LBFGS_STOP_OPT_AT_ENTRY = 1, /* max|g| <= tolerance_grad, first closure */
+    SGC_LBFGS_STOP_MAX_ITER = 2,     /* max_iter iterations taken               */
+    SGC_LBFGS_STOP_MAX_EVAL = 3,     /* max_eval closures consumed              */
+    SGC_LBFGS_STOP_OPT = 4,          /* max|g| <= tolerance_grad                */
+    SGC_LBFGS_STOP_GTD = 5,          /* g.d > -tolerance_change, no update      */
+    SGC_LBFGS_STOP_STEP_SMALL = 6,   /* max|t d| <= tolerance_change            */
+    SGC_LBFGS_STOP_LOSS_CHANGE = 7   /* |loss - prev_loss| < tolerance_change   */
+};
+int64_t sgc_lbfgs_workspace(int64_t n, int32_t history_size);
+int sgc_lbfgs_init(void *state, int64_t state_bytes, int64_t n, int32_t history_size,
+                   void *stream);
+int sgc_lbfgs_begin_step(void *state, void *stream);
+int sgc_lbfgs_iterate_f32(void *state, int32_t n_tensors, float *const *param_ptrs_host,
+                          const float *const *grad_ptrs_host, const int64_t *numels_host,
+                          const float *loss, double lr, int32_t max_iter, int32_t max_eval,
+                          double tolerance_grad, double tolerance_change, void *stream);
+int sgc_lbfgs_read_status(const void *state, int64_t *out_host, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Host (CPU) twins, for CPU tensors: the reference runs utils.py:92-97 on the
  * CPU whenever CUDA is off (args.py:39 --no-cuda; load_citation(cuda=False)).
  * Every pointer here is a HOST pointer; the calls are synchronous and
@@ -626,7 +689,7 @@ int sgc_mgpu_finalize(void);
  * `stream` (the current device) and waits for them, so those loads happen
  * here rather than inside the first sgc_precompute the caller times
  * (reddit.py:43,72-74).  Units: SGC_WARM_PROPAGATE = SpMM, ingest, plan,
- * sort, column groups, the exchanges' block copy; SGC_WARM_CLASSIFIER = linear, fused loss, cross-entropy;
+ * sort, column groups, the exchanges' block copy; SGC_WARM_CLASSIFIER = linear, fused loss, cross-entropy, L-BFGS;
  * SGC_WARM_LOADERS = normalisation, sub-graph.  Synchronous. */
 enum { SGC_WARM_PROPAGATE = 1, SGC_WARM_CLASSIFIER = 2, SGC_WARM_LOADERS = 4 };
 int sgc_warmup(uint32_t units, void *stream);

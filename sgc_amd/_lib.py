@@ -107,6 +107,12 @@ SIGNATURES = {
     "sgc_linear_backward_workspace": (_i64, [_i64, _i64, _i64]),
     "sgc_linear_backward_f32": (ctypes.c_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p,
                                                _i64, _p]),
+    "sgc_lbfgs_workspace": (_i64, [_i64, _i32]),
+    "sgc_lbfgs_init": (ctypes.c_int, [_p, _i64, _i64, _i32, _p]),
+    "sgc_lbfgs_begin_step": (ctypes.c_int, [_p, _p]),
+    "sgc_lbfgs_iterate_f32": (ctypes.c_int, [_p, _i32, _p, _p, _p, _p, ctypes.c_double, _i32, _i32,
+                                             ctypes.c_double, ctypes.c_double, _p]),
+    "sgc_lbfgs_read_status": (ctypes.c_int, [_p, ctypes.POINTER(_i64), _p]),
 }
 
 ABI_VERSION = 1

@@ -121,6 +121,13 @@ int mgpu_attach(const int32_t *row_ptr, const int32_t *col_idx, const float *val
 int mgpu_detach(int64_t handle);
 int mgpu_propagate(int64_t handle, const float *X, int64_t ldx, float *Y, int64_t ldy, int64_t F,
                    int32_t K, hipStream_t stream);
+int64_t lbfgs_workspace(int64_t n, int32_t history_size);
+int lbfgs_init(void *state, int64_t bytes, int64_t n, int32_t history_size, hipStream_t s);
+int lbfgs_begin_step(void *state, hipStream_t s);
+int lbfgs_iterate(void *state, int32_t n_tensors, float *const *params, const float *const *grads,
+                  const int64_t *numels, const float *loss, double lr, int32_t max_iter,
+                  int32_t max_eval, double tol_grad, double tol_change, hipStream_t s);
+int lbfgs_read_status(const void *state, int64_t *out_host, hipStream_t s);
 
 }  // namespace sgc
 
@@ -576,6 +583,31 @@ int sgc_linear_xent_f32(const float *X, int64_t ldx, const float *W, const float
                            workspace_bytes, as_stream(stream));
 }
 
+int64_t sgc_lbfgs_workspace(int64_t n, int32_t history_size) {
+    return lbfgs_workspace(n, history_size);
+}
+
+int sgc_lbfgs_init(void *state, int64_t state_bytes, int64_t n, int32_t history_size,
+                   void *stream) {
+    return lbfgs_init(state, state_bytes, n, history_size, as_stream(stream));
+}
+
+int sgc_lbfgs_begin_step(void *state, void *stream) {
+    return lbfgs_begin_step(state, as_stream(stream));
+}
+
+int sgc_lbfgs_iterate_f32(void *state, int32_t n_tensors, float *const *param_ptrs_host,
+                          const float *const *grad_ptrs_host, const int64_t *numels_host,
+                          const float *loss, double lr, int32_t max_iter, int32_t max_eval,
+                          double tolerance_grad, double tolerance_change, void *stream) {
+    return lbfgs_iterate(state, n_tensors, param_ptrs_host, grad_ptrs_host, numels_host, loss, lr,
+                         max_iter, max_eval, tolerance_grad, tolerance_change, as_stream(stream));
+}
+
+int sgc_lbfgs_read_status(const void *state, int64_t *out_host, void *stream) {
+    return lbfgs_read_status(state, out_host, as_stream(stream));
+}
+
 int sgc_warmup(uint32_t units, void *stream) {
     SGC_REQUIRE((units & ~7u) == 0, SGC_EINVAL, "warmup: unknown unit bits 0x%x", units);
     hipStream_t s = as_stream(stream);
@@ -592,6 +624,7 @@ int sgc_warmup(uint32_t units, void *stream) {
         SGC_HIP_CHECK(warm_linear(s));
         SGC_HIP_CHECK(warm_xent(s));
         SGC_HIP_CHECK(warm_loss(s));
+        SGC_HIP_CHECK(warm_lbfgs(s));
     }
     if (units & SGC_WARM_LOADERS) {
         SGC_HIP_CHECK(warm_normalize(s));
