@@ -287,6 +287,24 @@ int sgc_spmm_csr_f32_ex(const int32_t *row_ptr, const int32_t *col_idx, const fl
                         const int32_t *plan, int64_t n_heavy, int64_t n_hub,
                         int32_t heavy_threshold, uint32_t flags, void *stream);
 
+/* sgc_spmm_csr_f32_ex with the plan's count of rows that have at least one
+ * nonzero (n_nonempty = counts_host[3] of sgc_plan_sorted_ex; < 0 = unknown,
+ * which is sgc_spmm_csr_f32_ex).  It matters to SGC_SPMM_ACCUMULATE launches
+ * with SGC_SPMM_LIGHT_ORDER: they leave rows without nonzeros untouched, the
+ * plan lists those rows last, so the multi-row kernel's light items stop at
+ * n_nonempty - n_heavy and no wave is started for an empty row (the one-row
+ * kernel keeps its row order over all rows: measured faster there; a column
+ * group's accumulate pass at Reddit shape: 12 % of the rows in the pure split,
+ * 73 % with whole rows of <= 32 nonzeros, sgc_csr_colsplit_ex).  Plain
+ * launches cover every row as before (an empty row is written as zeros).
+ * A schedule only: the results are those of sgc_spmm_csr_f32_ex. */
+int sgc_spmm_csr_f32_ex2(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
+                         int64_t row_begin, int64_t row_end,
+                         const float *X, int64_t ldx, float *Y, int64_t ldy, int64_t F,
+                         const int32_t *plan, int64_t n_heavy, int64_t n_hub,
+                         int32_t heavy_threshold, uint32_t flags, int64_t n_nonempty,
+                         void *stream);
+
 /* K hops X_K = S^K X_0 over all n_rows rows (utils.py:92-97, the whole
  * sgc_precompute loop).  out (row stride ldo) receives X_K.  Intermediate
  * hops live in the workspace with 128-B aligned rows (ld = F rounded up to 32
@@ -395,6 +413,13 @@ int sgc_launch_list_add_spmm(int64_t handle, const int32_t *row_ptr, const int32
                              const int32_t *plan, int64_t n_heavy, int64_t n_hub,
                              int32_t heavy_threshold, uint32_t flags, int32_t x_slot,
                              int32_t y_slot);
+/* (records an sgc_spmm_csr_f32_ex2 launch: n_nonempty as there) */
+int sgc_launch_list_add_spmm_ex2(int64_t handle, const int32_t *row_ptr,
+                                 const int32_t *col_idx, const float *val, int64_t row_begin,
+                                 int64_t row_end, const float *X, int64_t ldx, float *Y,
+                                 int64_t ldy, int64_t F, const int32_t *plan, int64_t n_heavy,
+                                 int64_t n_hub, int32_t heavy_threshold, uint32_t flags,
+                                 int64_t n_nonempty, int32_t x_slot, int32_t y_slot);
 int sgc_launch_list_add_pad_rows(int64_t handle, const float *src, int64_t lds, float *dst,
                                  int64_t ldd, int64_t n_rows, int64_t F, int32_t src_slot,
                                  int32_t dst_slot);
@@ -629,6 +654,13 @@ int64_t sgc_plan_sorted_workspace(int64_t n_rows);
 int sgc_plan_sorted(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
                     int32_t threshold, int32_t hub_threshold, int32_t *plan, void *workspace,
                     int64_t workspace_bytes, int64_t *counts_host, void *stream);
+/* The same with a fourth count: counts_host[3] = rows of the range with at
+ * least one nonzero.  The sorted plan's empty rows are its tail, so an
+ * SGC_SPMM_ACCUMULATE launch given this count (sgc_spmm_csr_f32_ex2) stops
+ * before them.  counts_host holds four values here. */
+int sgc_plan_sorted_ex(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
+                       int32_t threshold, int32_t hub_threshold, int32_t *plan, void *workspace,
+                       int64_t workspace_bytes, int64_t *counts_host, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Column groups of S (a schedule for the SpMM of utils.py:95; results
@@ -646,12 +678,24 @@ int sgc_plan_sorted(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
  *             ordinary CSR for sgc_spmm_csr_f32_ex / sgc_plan_sorted;
  *   col_out / val_out: [nnz];  G <= 8;  asynchronous on `stream`;
  *   workspace: sgc_colsplit_workspace(n_rows, G) bytes on the device.
+ * sgc_csr_colsplit_ex, whole_rows = T >= 0: a row of at most T nonzeros is not
+ * cut -- its entire run goes to group 0, whatever its columns, and groups 1..
+ * hold nothing of it.  A group costs per row (a wave slot, a read + write of
+ * the row's partial sums, one more latency chain) and gains per gathered
+ * nonzero; short rows are most rows and few nonzeros, and a whole row in
+ * group 0 is that row's CSR chain in one launch, so the bits are the same.
+ * Same layout and workspace; sgc_csr_colsplit is whole_rows = 0.
  * ------------------------------------------------------------------------- */
 int64_t sgc_colsplit_workspace(int64_t n_rows, int32_t groups);
 int sgc_csr_colsplit(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
                      int64_t n_rows, int64_t n_cols, int32_t groups, const int32_t *cuts_host,
                      int32_t *row_ptrs, int32_t *col_out, float *val_out, void *workspace,
                      int64_t workspace_bytes, void *stream);
+int sgc_csr_colsplit_ex(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
+                        int64_t n_rows, int64_t n_cols, int32_t groups,
+                        const int32_t *cuts_host, int32_t whole_rows, int32_t *row_ptrs,
+                        int32_t *col_out, float *val_out, void *workspace,
+                        int64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
  * One process, several GPUs (the multi-GPU form of the one

@@ -46,6 +46,8 @@ SIGNATURES = {
                                         _p, _i64, _i64, _i32, _p]),
     "sgc_spmm_csr_f32_ex": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _i64,
                                            _p, _i64, _i64, _i32, _u32, _p]),
+    "sgc_spmm_csr_f32_ex2": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _i64,
+                                            _p, _i64, _i64, _i32, _u32, _i64, _p]),
     "sgc_propagate_workspace": (_i64, [_i64, _i64, _i64, _i32]),
     "sgc_propagate_f32": (ctypes.c_int, [_p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i32,
                                          _p, _i64, _i64, _i32, _p, _i64, _p]),
@@ -66,6 +68,9 @@ SIGNATURES = {
     "sgc_launch_list_create": (ctypes.c_int, [ctypes.POINTER(_i64)]),
     "sgc_launch_list_add_spmm": (ctypes.c_int, [_i64, _p, _p, _p, _i64, _i64, _p, _i64, _p, _i64,
                                                 _i64, _p, _i64, _i64, _i32, _u32, _i32, _i32]),
+    "sgc_launch_list_add_spmm_ex2": (ctypes.c_int, [_i64, _p, _p, _p, _i64, _i64, _p, _i64, _p,
+                                                    _i64, _i64, _p, _i64, _i64, _i32, _u32, _i64,
+                                                    _i32, _i32]),
     "sgc_launch_list_add_pad_rows": (ctypes.c_int, [_i64, _p, _i64, _p, _i64, _i64, _i64, _i32,
                                                     _i32]),
     "sgc_launch_list_run": (ctypes.c_int, [_i64, _p, _p, _p]),
@@ -96,8 +101,11 @@ SIGNATURES = {
     "sgc_colsplit_workspace": (_i64, [_i64, _i32]),
     "sgc_csr_colsplit": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _i64,
                                         _p]),
+    "sgc_csr_colsplit_ex": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i32, _p, _i32, _p, _p, _p, _p,
+                                           _i64, _p]),
     "sgc_plan_sorted_workspace": (_i64, [_i64]),
     "sgc_plan_sorted": (ctypes.c_int, [_p, _i64, _i64, _i32, _i32, _p, _p, _i64, _p, _p]),
+    "sgc_plan_sorted_ex": (ctypes.c_int, [_p, _i64, _i64, _i32, _i32, _p, _p, _i64, _p, _p]),
     "sgc_mgpu_init": (ctypes.c_int, [ctypes.c_int, _p]),
     "sgc_mgpu_attach": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _p, ctypes.POINTER(_i64)]),
     "sgc_mgpu_propagate": (ctypes.c_int, [_i64, _p, _i64, _p, _i64, _i64, _i32, _p]),

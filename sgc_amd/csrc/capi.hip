@@ -34,7 +34,8 @@ int light_order(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int3
 int launch_spmm(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
                 int64_t row_begin, int64_t row_end, const float *X, int64_t ldx, float *Y,
                 int64_t ldy, int64_t F, const int32_t *heavy_rows, int64_t n_heavy,
-                int64_t n_hub, int32_t heavy_threshold, uint32_t flags, hipStream_t stream);
+                int64_t n_hub, int32_t heavy_threshold, uint32_t flags, hipStream_t stream,
+                int64_t n_nonempty = -1);
 int launch_spmm_x16(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
                     int64_t row_begin, int64_t row_end, const void *X, int32_t x_dtype,
                     int64_t ldx, void *Y, int32_t y_dtype, int64_t ldy, int64_t F,
@@ -109,11 +110,18 @@ int64_t plan_sorted_workspace(int64_t n_rows);
 int plan_sorted(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
                 int32_t hub_threshold, int32_t *plan, void *workspace, int64_t workspace_bytes,
                 int64_t *counts_host, hipStream_t stream);
+int plan_sorted_ex(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
+                   int32_t hub_threshold, int32_t *plan, void *workspace,
+                   int64_t workspace_bytes, int64_t *counts_host, hipStream_t stream);
 int64_t colsplit_workspace(int64_t n_rows, int32_t groups);
 int colsplit(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n_rows,
              int64_t n_cols, int32_t groups, const int32_t *cuts_host, int32_t *row_ptrs,
              int32_t *col_out, float *val_out, void *workspace, int64_t workspace_bytes,
              hipStream_t stream);
+int colsplit_ex(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n_rows,
+                int64_t n_cols, int32_t groups, const int32_t *cuts_host, int32_t whole_rows,
+                int32_t *row_ptrs, int32_t *col_out, float *val_out, void *workspace,
+                int64_t workspace_bytes, hipStream_t stream);
 int mgpu_init(int ndev, const int *devices);
 int mgpu_finalize();
 int mgpu_attach(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n,
@@ -238,6 +246,10 @@ int sgc_spmm_csr_f32(const int32_t *row_ptr, const int32_t *col_idx, const float
                        as_stream(stream));
 }
 
+static constexpr uint32_t kSpmmFlags =
+    SGC_SPMM_X_PADDED | SGC_SPMM_Y_PADDED | SGC_SPMM_NO_HUB | SGC_SPMM_HUB_ONLY |
+    SGC_SPMM_ACCUMULATE | SGC_SPMM_HUB_SERIAL | SGC_SPMM_LIGHT_ORDER | SGC_SPMM_X_UNDER_4G;
+
 int sgc_spmm_csr_f32_ex(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
                         int64_t row_begin, int64_t row_end, const float *X, int64_t ldx, float *Y,
                         int64_t ldy, int64_t F, const int32_t *plan, int64_t n_heavy,
@@ -251,6 +263,19 @@ int sgc_spmm_csr_f32_ex(const int32_t *row_ptr, const int32_t *col_idx, const fl
     return launch_spmm(row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F, plan,
                        plan ? n_heavy : 0, plan ? n_hub : 0, heavy_threshold, flags,
                        as_stream(stream));
+}
+
+int sgc_spmm_csr_f32_ex2(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
+                         int64_t row_begin, int64_t row_end, const float *X, int64_t ldx,
+                         float *Y, int64_t ldy, int64_t F, const int32_t *plan, int64_t n_heavy,
+                         int64_t n_hub, int32_t heavy_threshold, uint32_t flags,
+                         int64_t n_nonempty, void *stream) {
+    SGC_REQUIRE((flags & ~kSpmmFlags) == 0, SGC_EINVAL, "spmm_ex2: unknown flags 0x%x", flags);
+    SGC_REQUIRE(!((flags & SGC_SPMM_NO_HUB) && (flags & SGC_SPMM_HUB_ONLY)), SGC_EINVAL,
+                "spmm_ex2: NO_HUB and HUB_ONLY together");
+    return launch_spmm(row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F, plan,
+                       plan ? n_heavy : 0, plan ? n_hub : 0, heavy_threshold, flags,
+                       as_stream(stream), plan ? n_nonempty : -1);
 }
 
 int sgc_spmm_csr_x16(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
@@ -339,6 +364,7 @@ struct ListOp {
     int32_t threshold;
     uint32_t flags;
     int32_t x_slot, y_slot;  // SGC_SLOT_*: the pointer as recorded, or the run's X_0 / X_K
+    int64_t n_nonempty = -1;  // the plan's rows with nonzeros (sgc_spmm_csr_f32_ex2), -1 unknown
 };
 
 struct LaunchList {
@@ -409,6 +435,22 @@ int sgc_launch_list_add_spmm(int64_t handle, const int32_t *row_ptr, const int32
                                    flags, x_slot, y_slot});
 }
 
+int sgc_launch_list_add_spmm_ex2(int64_t handle, const int32_t *row_ptr, const int32_t *col_idx,
+                                 const float *val, int64_t row_begin, int64_t row_end,
+                                 const float *X, int64_t ldx, float *Y, int64_t ldy, int64_t F,
+                                 const int32_t *plan, int64_t n_heavy, int64_t n_hub,
+                                 int32_t heavy_threshold, uint32_t flags, int64_t n_nonempty,
+                                 int32_t x_slot, int32_t y_slot) {
+    SGC_REQUIRE((flags & ~kSpmmFlags) == 0, SGC_EINVAL,
+                "launch_list_add_spmm: unknown flags 0x%x", flags);
+    SGC_REQUIRE(!((flags & SGC_SPMM_NO_HUB) && (flags & SGC_SPMM_HUB_ONLY)), SGC_EINVAL,
+                "launch_list_add_spmm: NO_HUB and HUB_ONLY together");
+    ListOp op{0, row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F, plan,
+              plan ? n_heavy : 0, plan ? n_hub : 0, heavy_threshold, flags, x_slot, y_slot};
+    op.n_nonempty = plan ? n_nonempty : -1;
+    return list_add(handle, op);
+}
+
 int sgc_launch_list_add_pad_rows(int64_t handle, const float *src, int64_t lds, float *dst,
                                  int64_t ldd, int64_t n_rows, int64_t F, int32_t src_slot,
                                  int32_t dst_slot) {
@@ -443,7 +485,7 @@ int sgc_launch_list_run(int64_t handle, const float *X0, float *out, void *strea
         }
         rc = op.kind == 0 ? launch_spmm(op.row_ptr, op.col_idx, op.val, op.row_begin, op.row_end, x,
                                         op.ldx, y, op.ldy, op.F, op.plan, op.n_heavy, op.n_hub,
-                                        op.threshold, op.flags, s)
+                                        op.threshold, op.flags, s, op.n_nonempty)
                           : launch_pad_rows(x, op.ldx, y, op.ldy, op.row_end, op.F, s);
         if (rc != SGC_OK) break;
     }
@@ -715,6 +757,14 @@ int sgc_csr_colsplit(const int32_t *row_ptr, const int32_t *col_idx, const float
                     val_out, workspace, workspace_bytes, as_stream(stream));
 }
 
+int sgc_csr_colsplit_ex(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
+                        int64_t n_rows, int64_t n_cols, int32_t groups, const int32_t *cuts_host,
+                        int32_t whole_rows, int32_t *row_ptrs, int32_t *col_out, float *val_out,
+                        void *workspace, int64_t workspace_bytes, void *stream) {
+    return colsplit_ex(row_ptr, col_idx, val, n_rows, n_cols, groups, cuts_host, whole_rows,
+                       row_ptrs, col_out, val_out, workspace, workspace_bytes, as_stream(stream));
+}
+
 int64_t sgc_plan_sorted_workspace(int64_t n_rows) { return plan_sorted_workspace(n_rows); }
 
 int sgc_plan_sorted(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
@@ -722,4 +772,11 @@ int sgc_plan_sorted(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
                     int64_t workspace_bytes, int64_t *counts_host, void *stream) {
     return plan_sorted(row_ptr, row_begin, row_end, threshold, hub_threshold, plan, workspace,
                        workspace_bytes, counts_host, as_stream(stream));
+}
+
+int sgc_plan_sorted_ex(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
+                       int32_t threshold, int32_t hub_threshold, int32_t *plan, void *workspace,
+                       int64_t workspace_bytes, int64_t *counts_host, void *stream) {
+    return plan_sorted_ex(row_ptr, row_begin, row_end, threshold, hub_threshold, plan, workspace,
+                          workspace_bytes, counts_host, as_stream(stream));
 }

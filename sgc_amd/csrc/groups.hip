@@ -16,6 +16,20 @@
 // (group 0's runs of rows 0..n-1, then group 1's, ...); group g's row_ptr
 // holds absolute offsets into it, so (row_ptr_g, col, val) is an ordinary
 // CSR the SpMM, the plan and the hub kernel take unchanged.
+//
+// Whole rows (colsplit_ex, whole_rows = T): a row of at most T nonzeros is
+// not cut -- its entire run goes to group 0, whatever its columns, and it is
+// empty in groups 1..  The price of a group is paid per row (a wave slot, one
+// read + write of the row's partial sums, a second latency chain for a run of
+// a few nonzeros) while its gain is per gathered nonzero, and short rows hold
+// most rows but few nonzeros (Reddit shape: rows of <= 32 nonzeros are 73 %
+// of the rows and 5.9 % of the nonzeros).  A whole row in group 0 is that
+// row's CSR chain in one launch: the same bits.  T = 0 is the pure split.
+// Measured (interleaved, bit-identical, profiles/whole_rows/): Reddit shape,
+// G = 2, one hop at 602 floats 3.71 -> 3.59 ms at T = 32 and the K = 2 step
+// 7.98 -> 7.60; RMAT shape, G = 4, the K = 3 step 88.2 -> 85.6 ms.  The
+// Python layer's rule is T = 32 (propagate.GROUP_WHOLE_ROWS_RULE); the
+// multi-device engine's split (mgpu.hip) stays at T = 0.
 #include "common.h"
 
 #include <algorithm>
@@ -46,7 +60,8 @@ __device__ __forceinline__ int32_t lower_bound(const int32_t *__restrict__ col, 
 // per-row counts of every group (counts[g * n + r]) and per-block totals
 __global__ void colsplit_count_kernel(const int32_t *__restrict__ row_ptr,
                                       const int32_t *__restrict__ col, int32_t n, int32_t chunk,
-                                      int G, Cuts cuts, int32_t *__restrict__ counts,
+                                      int G, Cuts cuts, int32_t whole_rows,
+                                      int32_t *__restrict__ counts,
                                       int32_t *__restrict__ block_sums) {
     __shared__ int32_t s_sum[kGroupsMax];
     if (threadIdx.x < kGroupsMax) s_sum[threadIdx.x] = 0;
@@ -55,9 +70,11 @@ __global__ void colsplit_count_kernel(const int32_t *__restrict__ row_ptr,
     int32_t mine[kGroupsMax] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int32_t r = r0 + threadIdx.x; r < r1; r += blockDim.x) {
         const int32_t k0 = row_ptr[r], k1 = row_ptr[r + 1];
+        const bool whole = k1 - k0 <= whole_rows;  // a short row stays in group 0
         int32_t lo = k0;
         for (int g = 0; g < G; ++g) {
-            const int32_t hi = (g + 1 == G) ? k1 : lower_bound(col, lo, k1, cuts.c[g + 1]);
+            const int32_t hi =
+                (whole || g + 1 == G) ? k1 : lower_bound(col, lo, k1, cuts.c[g + 1]);
             counts[(int64_t)g * n + r] = hi - lo;
             mine[g] += hi - lo;
             lo = hi;
@@ -123,13 +140,21 @@ __global__ void colsplit_rowptr_kernel(const int32_t *__restrict__ counts, int32
 __global__ void colsplit_fill_kernel(const int32_t *__restrict__ row_ptr,
                                      const int32_t *__restrict__ col,
                                      const float *__restrict__ val, int32_t n, int G, Cuts cuts,
-                                     const int32_t *__restrict__ row_ptrs,
+                                     int32_t whole_rows, const int32_t *__restrict__ row_ptrs,
                                      int32_t *__restrict__ col_out, float *__restrict__ val_out) {
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t waves = (int64_t)gridDim.x * (blockDim.x / kWave);
     for (int64_t r = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave; r < n;
          r += waves) {
         const int32_t k0 = row_ptr[r], k1 = row_ptr[r + 1];
+        if (k1 - k0 <= whole_rows) {  // wave-uniform: the whole run is group 0's
+            const int32_t dst = row_ptrs[r];
+            for (int32_t k = k0 + lane; k < k1; k += kWave) {
+                col_out[dst + (k - k0)] = col[k];
+                val_out[dst + (k - k0)] = val[k];
+            }
+            continue;
+        }
         int32_t lo = k0;
         for (int g = 0; g < G; ++g) {
             const int32_t hi = (g + 1 == G) ? k1 : lower_bound(col, lo, k1, cuts.c[g + 1]);
@@ -156,10 +181,11 @@ int64_t colsplit_workspace(int64_t n_rows, int32_t groups) {
                      up((size_t)groups * nblocks(n_rows) * sizeof(int32_t)));
 }
 
-int colsplit(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n_rows,
-             int64_t n_cols, int32_t groups, const int32_t *cuts_host, int32_t *row_ptrs,
-             int32_t *col_out, float *val_out, void *workspace, int64_t workspace_bytes,
-             hipStream_t stream) {
+int colsplit_ex(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n_rows,
+                int64_t n_cols, int32_t groups, const int32_t *cuts_host, int32_t whole_rows,
+                int32_t *row_ptrs, int32_t *col_out, float *val_out, void *workspace,
+                int64_t workspace_bytes, hipStream_t stream) {
+    SGC_REQUIRE(whole_rows >= 0, SGC_EINVAL, "colsplit: whole_rows must be >= 0");
     SGC_REQUIRE(groups >= 1 && groups <= kGroupsMax, SGC_EINVAL,
                 "colsplit: groups must be 1..%d", kGroupsMax);
     SGC_REQUIRE(n_rows >= 0 && n_rows < INT32_MAX && n_cols >= 0 && n_cols < INT32_MAX,
@@ -191,7 +217,7 @@ int colsplit(const int32_t *row_ptr, const int32_t *col_idx, const float *val, i
     w += up((size_t)groups * n_rows * sizeof(int32_t));
     int32_t *block_sums = reinterpret_cast<int32_t *>(w);
     hipLaunchKernelGGL(colsplit_count_kernel, dim3(nblk), dim3(kThreads), 0, stream, row_ptr,
-                       col_idx, n, chunk, (int)groups, cuts, counts, block_sums);
+                       col_idx, n, chunk, (int)groups, cuts, whole_rows, counts, block_sums);
     SGC_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(colsplit_scan_blocks_kernel, dim3(1), dim3(kWave), 0, stream, block_sums,
                        nblk, (int)groups);
@@ -201,9 +227,18 @@ int colsplit(const int32_t *row_ptr, const int32_t *col_idx, const float *val, i
     SGC_HIP_CHECK(hipGetLastError());
     const int fill_blocks = (int)std::min<int64_t>((n_rows + 3) / 4, 8192);
     hipLaunchKernelGGL(colsplit_fill_kernel, dim3(fill_blocks), dim3(kThreads), 0, stream, row_ptr,
-                       col_idx, val, n, (int)groups, cuts, row_ptrs, col_out, val_out);
+                       col_idx, val, n, (int)groups, cuts, whole_rows, row_ptrs, col_out, val_out);
     SGC_HIP_CHECK(hipGetLastError());
     return SGC_OK;
+}
+
+// the pure split: every row cut at the column cuts (whole_rows = 0)
+int colsplit(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n_rows,
+             int64_t n_cols, int32_t groups, const int32_t *cuts_host, int32_t *row_ptrs,
+             int32_t *col_out, float *val_out, void *workspace, int64_t workspace_bytes,
+             hipStream_t stream) {
+    return colsplit_ex(row_ptr, col_idx, val, n_rows, n_cols, groups, cuts_host, 0, row_ptrs,
+                       col_out, val_out, workspace, workspace_bytes, stream);
 }
 
 // Every row's columns strictly ascending?  (the ingest's status bit 2 for a

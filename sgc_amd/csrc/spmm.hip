@@ -1027,7 +1027,7 @@ struct LaunchArgs {
     int accum;
     hipStream_t stream;
     const int *light_rows;  // SGC_SPMM_LIGHT_ORDER: the light rows in processing order, or null
-    int n_light;
+    int n_light;            // light items of that order (an accumulate launch: those with nonzeros)
     // fused rows + hub launch (spmm_rows_kernel HF = 32): the hub rows and items
     const int *hub_rows = nullptr;
     int hub_chunks = 0, n_hub_blocks = 0;
@@ -1198,6 +1198,13 @@ hipError_t launch_vc(const LaunchArgs &a) {
     constexpr int U = U0;
     constexpr int UH = kHeavyU;
     constexpr int VH = (SGC_HEAVY_VEC < V) ? SGC_HEAVY_VEC : V;
+    // light items: every row in row order (non-light rows skip themselves),
+    // accumulate launches too.  Taking an accumulate launch's light rows with
+    // nonzeros from the plan instead (length order, as the multi-row kernel
+    // does) measured slower here: RMAT shape, G = 4, one hop 29.29 -> 31.62 ms
+    // in the pure split and 28.58 -> 28.63 with whole rows of <= 32 nonzeros
+    // (profiles/whole_rows/sweep_rmat_allrows.log) -- a wave per row leaves
+    // nothing to pack, and in row order the partial sums stream.
     const int64_t waves = (int64_t)a.n_heavy * (C * V / VH) + a.n_rows;
     const int64_t blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock + (HF ? a.n_hub_blocks : 0);
     if (blocks >= INT32_MAX) return hipErrorInvalidValue;
@@ -1253,11 +1260,13 @@ hipError_t launch_rows(const LaunchArgs &a, int F_load, int LR, int vec_store) {
                       : slices > 1 ? SW / (kWave * VH) : (F_load + kWave * VH - 1) / (kWave * VH);
     const int64_t heavy_waves = (int64_t)a.n_heavy * n_sub;
     // light items: every row (non-light rows skip themselves), or with a
-    // light order exactly the light rows
+    // light order exactly the light rows (an accumulate launch: the light
+    // rows with nonzeros, the order's head)
     const int n_light_items = a.light_rows ? a.n_light : a.n_rows;
     const int64_t waves = heavy_waves + (n_light_items + R - 1) / R;
     const int64_t blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock + (HF ? a.n_hub_blocks : 0);
     if (blocks >= INT32_MAX) return hipErrorInvalidValue;
+    if (blocks == 0) return hipSuccess;  // an accumulate launch over empty runs
     dim3 grid((unsigned)blocks, (unsigned)slices);
     hipLaunchKernelGGL((spmm_rows_kernel<LB, VH, kHeavyU, O32, QV, HF>), grid, dim3(kBlock), 0,
                        a.stream, a.row_ptr, a.col, a.val, a.X, a.ldx, a.Y, a.ldy, a.row_begin,
@@ -1451,7 +1460,8 @@ int64_t get_tuning(const char *key) {
 int launch_spmm(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
                 int64_t row_begin, int64_t row_end, const float *X, int64_t ldx, float *Y,
                 int64_t ldy, int64_t F, const int32_t *heavy_rows, int64_t n_heavy,
-                int64_t n_hub, int32_t heavy_threshold, uint32_t flags, hipStream_t stream) {
+                int64_t n_hub, int32_t heavy_threshold, uint32_t flags, hipStream_t stream,
+                int64_t n_nonempty) {
     // col_idx / val may be NULL for a CSR without nonzeros (torch's empty
     // tensors have no storage): the kernels never dereference them then
     SGC_REQUIRE(row_ptr && X && Y, SGC_EINVAL, "spmm: null pointer");
@@ -1471,6 +1481,18 @@ int launch_spmm(const int32_t *row_ptr, const int32_t *col_idx, const float *val
         SGC_REQUIRE(n_heavy <= n_rows, SGC_EINVAL, "spmm: light order with n_heavy > rows");
         light_rows = heavy_rows + n_heavy;
         n_light = n_rows - n_heavy;
+    }
+    // An accumulate launch leaves rows without nonzeros untouched, and the
+    // plan is sorted longest first: with the plan's count of rows that have
+    // nonzeros (n_nonempty >= 0; heavy rows are among them) the light items
+    // stop where the empty rows begin -- no wave is started for them (the
+    // multi-row kernel; the one-row kernel keeps row order over all rows,
+    // launch_vc).  A plain launch covers every row (an empty row is written
+    // as zeros).
+    if (light_rows && (flags & SGC_SPMM_ACCUMULATE) && n_nonempty >= 0) {
+        SGC_REQUIRE(n_nonempty >= n_heavy && n_nonempty <= n_rows, SGC_EINVAL,
+                    "spmm: n_nonempty %lld outside [n_heavy, rows]", (long long)n_nonempty);
+        n_light = n_nonempty - n_heavy;
     }
     if (!heavy_rows) {
         n_heavy = 0;

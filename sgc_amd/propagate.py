@@ -63,6 +63,16 @@ class Plan(NamedTuple):
     threshold: int
     max_hub_degree: int = 0  # nonzeros of the longest hub row (0: no hub rows)
     ordered: bool = False  # rows also lists the light rows, longest first (SPMM_LIGHT_ORDER)
+    n_nonempty: int = -1  # rows with at least one nonzero (sgc_plan_sorted_ex); -1: not counted
+
+    @property
+    def accumulate_light_items(self):
+        """Light items of an SPMM_ACCUMULATE launch with this plan: the light
+        rows that have nonzeros (the sorted plan's empty rows are its tail and
+        get no wave), or None when the launch covers every row."""
+        if not self.ordered or self.n_nonempty < 0:
+            return None
+        return self.n_nonempty - self.n_heavy
 
     def hub_flags(self):
         """The plan's launch flags: SPMM_HUB_SERIAL when the hub kernel is
@@ -116,11 +126,39 @@ STATUS_OUT_OF_RANGE = 4
 # 152 / 256 (the one-row kernel) 1.56 -> 1.58 / 1.85 -> 1.88;
 # RMAT shape (F = 256) 31.4 -> 30.1 (G = 2) -> 29.5 ms (G = 4).  None set =
 # column_groups_for's size rule; SGC_AMD_COLUMN_GROUPS=G forces G (1 = off).
+# Short rows are not cut (GROUP_WHOLE_ROWS below): the price of a group is per
+# row, its gain per nonzero.
 _GROUPS_ENV = os.environ.get("SGC_AMD_COLUMN_GROUPS")
 COLUMN_GROUPS = int(_GROUPS_ENV) if _GROUPS_ENV else None
 GROUPS_MIN_NNZ = 1 << 22    # below: latency-bound launches, one launch per hop
 GROUPS_MIN_WIDTH = 128      # narrower launches gain nothing (76 floats: 0.77 vs 0.77 ms)
 GROUPS_WIDE_NNZ = 1 << 26   # from here four groups (RMAT shape)
+# Whole rows (sgc_csr_colsplit_ex): a row of at most T nonzeros is not cut; its
+# whole run stays in group 0 and the accumulate launches skip it (the plan's
+# count of rows with nonzeros bounds their light items).  A group costs per
+# row and gains per gathered nonzero, and short rows are most rows but few
+# nonzeros (Reddit shape: <= 32 nonzeros = 73 % of the rows, 5.9 % of the
+# nonzeros).  Same bits.  Measured interleaved, every point bit-identical
+# (scripts/whole_rows_ab.py, profiles/whole_rows/): Reddit shape, G = 2, the
+# K = 2 step at T = 0 / 8 / 16 / 32 / 64 / 96: 7.98 / 7.71 / 7.61 / 7.60 / 7.65 /
+# 7.80 ms (one hop at 602 floats 3.71 -> 3.59; the accumulate launch's light
+# rows 201,713 -> 58,235); G = 3 is best at T = 16 (7.51) and G = 4 at T = 64
+# (7.50), within 1.3 % of G = 2 at T = 32, so G stays.  RMAT shape, G = 4, the
+# K = 3 step 88.15 / 85.77 / 85.54 / 85.64 / 85.72 / 86.16 ms (G = 2: 90.1 ->
+# 89.0 at best).  T = 32 is the middle of both plateaus.  None = group_whole_rows_for's rule;
+# SGC_AMD_GROUP_WHOLE_ROWS=T forces T (0 = the pure split).
+_WHOLE_ENV = os.environ.get("SGC_AMD_GROUP_WHOLE_ROWS")
+GROUP_WHOLE_ROWS = int(_WHOLE_ENV) if _WHOLE_ENV else None
+GROUP_WHOLE_ROWS_RULE = 32
+
+
+def group_whole_rows_for(csr, G):
+    """T of the whole-row rule for G column groups of `csr`."""
+    if G <= 1:
+        return 0
+    if GROUP_WHOLE_ROWS is not None:
+        return max(0, int(GROUP_WHOLE_ROWS))
+    return GROUP_WHOLE_ROWS_RULE
 
 
 def column_groups_for(csr, width):
@@ -204,14 +242,20 @@ class DeviceCSR:
         """Column cuts of the G column groups: group g = columns [c_g, c_{g+1})."""
         return [(g * self.n_cols) // G for g in range(G + 1)]
 
-    def column_groups(self, G):
-        """The G column-group CSRs of this one (sgc_csr_colsplit; cached):
+    def column_groups(self, G, whole_rows=0):
+        """The G column-group CSRs of this one (sgc_csr_colsplit_ex; cached):
         columns cut at g * n_cols / G, every row's run of each group in its
         storage order; group g's row_ptr points into one shared col/val
-        copy.  Rows must have ascending columns."""
+        copy.  A row of at most `whole_rows` nonzeros is not cut: all of it
+        is in group 0 (0 = the pure split).  Rows must have ascending
+        columns."""
         if not self.cols_ascending:
             raise ValueError("sgc_amd: column groups need rows with ascending columns")
-        key = ("groups", int(G))
+        whole_rows = int(whole_rows)
+        if whole_rows < 0:
+            raise ValueError("sgc_amd: whole_rows must be >= 0")
+        whole_rows = min(whole_rows, 2 ** 31 - 1)
+        key = ("groups", int(G), whole_rows)
         if key not in self._plans:
             import ctypes
             lib = _lib.load()
@@ -223,12 +267,12 @@ class DeviceCSR:
             ws_bytes = lib.sgc_colsplit_workspace(n, G)
             ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=dev)
             with torch.cuda.device(dev):
-                _lib.check(lib.sgc_csr_colsplit(_lib.ptr(self.row_ptr), _lib.ptr(self.col_idx),
-                                                _lib.ptr(self.val), n, self.n_cols, G,
-                                                ctypes.cast(cuts, ctypes.c_void_p),
-                                                _lib.ptr(row_ptrs), _lib.ptr(col), _lib.ptr(val),
-                                                _lib.ptr(ws), ws_bytes,
-                                                _lib.stream_handle(dev)), "csr_colsplit")
+                _lib.check(lib.sgc_csr_colsplit_ex(_lib.ptr(self.row_ptr), _lib.ptr(self.col_idx),
+                                                   _lib.ptr(self.val), n, self.n_cols, G,
+                                                   ctypes.cast(cuts, ctypes.c_void_p), whole_rows,
+                                                   _lib.ptr(row_ptrs), _lib.ptr(col),
+                                                   _lib.ptr(val), _lib.ptr(ws), ws_bytes,
+                                                   _lib.stream_handle(dev)), "csr_colsplit")
             del ws  # stream-ordered: the allocator reuses it after the kernels
             self._plans[key] = [DeviceCSR(n, self.n_cols, row_ptrs[g], col[:nnz], val[:nnz],
                                           self.status) for g in range(G)]
@@ -244,20 +288,21 @@ class DeviceCSR:
 
     def drop_groups(self):
         """Free the cached column-group copies of S (and their plans): one
-        more col/val copy per G (188 MB at Reddit shape).  They are rebuilt
-        on the next launch that uses them."""
+        more col/val copy per (G, whole_rows) (188 MB at Reddit shape).  They
+        are rebuilt on the next launch that uses them."""
         self.release_prepared()  # recorded launch lists hold the groups' pointers
         for key in [k for k in self._plans if isinstance(k, tuple) and k[:1] == ("groups",)]:
             for part in self._plans.pop(key):
                 part._plans.clear()
 
     def groups_or_self(self, G):
-        """The G column-group CSRs, or [self] when G == 1 or when the copy
-        does not fit in device memory (a schedule: the results are the same)."""
+        """The G column-group CSRs under the whole-row rule
+        (group_whole_rows_for), or [self] when G == 1 or when the copy does
+        not fit in device memory (a schedule: the results are the same)."""
         if G <= 1:
             return [self]
         try:
-            return self.column_groups(G)
+            return self.column_groups(G, group_whole_rows_for(self, G))
         except torch.cuda.OutOfMemoryError:
             return [self]
 
@@ -433,14 +478,15 @@ class DeviceCSR:
         rows = torch.empty(max(1, n), dtype=torch.int32, device=self.device)
         ws_bytes = lib.sgc_plan_sorted_workspace(n)
         ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=self.device)
-        counts = (ctypes.c_int64 * 3)()
+        counts = (ctypes.c_int64 * 4)()
         with torch.cuda.device(self.device):
-            _lib.check(lib.sgc_plan_sorted(_lib.ptr(self.row_ptr), row_begin, row_end, threshold,
-                                           hub, _lib.ptr(rows), _lib.ptr(ws), ws_bytes,
-                                           ctypes.cast(counts, ctypes.c_void_p),
-                                           _lib.stream_handle(self.device)), "plan_sorted")
+            _lib.check(lib.sgc_plan_sorted_ex(_lib.ptr(self.row_ptr), row_begin, row_end,
+                                              threshold, hub, _lib.ptr(rows), _lib.ptr(ws),
+                                              ws_bytes, ctypes.cast(counts, ctypes.c_void_p),
+                                              _lib.stream_handle(self.device)), "plan_sorted")
         h, nh = int(counts[0]), int(counts[1])
-        return Plan(rows, h, nh, threshold, int(counts[2]) if nh > 0 else 0, n > h)
+        return Plan(rows, h, nh, threshold, int(counts[2]) if nh > 0 else 0, n > h,
+                    int(counts[3]))
 
 
 def to_torch_coo(csr: DeviceCSR):
@@ -701,14 +747,14 @@ def spmm(csr: DeviceCSR, X: torch.Tensor, row_begin=0, row_end=None, out=None,
         stream = _lib.stream_handle(X.device)
         for g, c in enumerate(parts):  # group 0 plain, groups 1.. continue its chains
             pl = c.plan(row_begin, row_end, threshold, hub_threshold, F) if use_plan else NO_PLAN
-            _lib.check(lib.sgc_spmm_csr_f32_ex(_lib.ptr(c.row_ptr), _lib.ptr(c.col_idx),
-                                               _lib.ptr(c.val), row_begin, row_end, _lib.ptr(X),
-                                               X.stride(0), _lib.ptr(out), out.stride(0), F,
-                                               _lib.ptr(pl.rows), pl.n_heavy, pl.n_hub,
-                                               pl.threshold,
-                                               int(flags) | pl.hub_flags() | x_flags(X) |
-                                               (SPMM_ACCUMULATE if g else 0), stream),
-                       "spmm_csr_f32")
+            _lib.check(lib.sgc_spmm_csr_f32_ex2(_lib.ptr(c.row_ptr), _lib.ptr(c.col_idx),
+                                                _lib.ptr(c.val), row_begin, row_end, _lib.ptr(X),
+                                                X.stride(0), _lib.ptr(out), out.stride(0), F,
+                                                _lib.ptr(pl.rows), pl.n_heavy, pl.n_hub,
+                                                pl.threshold,
+                                                int(flags) | pl.hub_flags() | x_flags(X) |
+                                                (SPMM_ACCUMULATE if g else 0), pl.n_nonempty,
+                                                stream), "spmm_csr_f32")
     return out
 
 
@@ -734,12 +780,12 @@ class SpmmLaunch:
         F = X.shape[1]
         pl = csr.plan(row_begin, row_end, threshold, hub_threshold, F)
         lib = _lib.load()
-        self._fn = lib.sgc_spmm_csr_f32_ex
+        self._fn = lib.sgc_spmm_csr_f32_ex2
         self._keep = (csr, X, out, pl) if keep_tensors else (csr, pl)
         self._args = (_lib.ptr(csr.row_ptr), _lib.ptr(csr.col_idx), _lib.ptr(csr.val),
                       int(row_begin), int(row_end), _lib.ptr(X), X.stride(0), _lib.ptr(out),
                       out.stride(0), F, _lib.ptr(pl.rows), pl.n_heavy, pl.n_hub, pl.threshold,
-                      int(flags) | pl.hub_flags() | x_flags(X))
+                      int(flags) | pl.hub_flags() | x_flags(X), pl.n_nonempty)
 
     def __call__(self, stream_handle):
         rc = self._fn(*self._args, stream_handle)
@@ -827,17 +873,19 @@ def propagate(csr: DeviceCSR, X: torch.Tensor, K: int, out=None, use_plan=True, 
     if (not native_loop and hop_hook is None and prepare and X.data_ptr() != out.data_ptr()
             and not torch.cuda.is_current_stream_capturing()):
         key = ("list", X.stride(0), F, int(K), out.stride(0), X.data_ptr() % 128 == 0,
-               threshold, hub_threshold, bool(use_plan), G_rule, stream, PAD_X0)
+               threshold, hub_threshold, bool(use_plan), G_rule,
+               group_whole_rows_for(csr, G_rule), stream, PAD_X0)
         prep = csr._plans.get(key)
         if prep is not None:
             rc = lib.sgc_launch_list_run(prep[1].handle, X.data_ptr(), out.data_ptr(), stream)
             if rc:
                 _lib.check(rc, "propagate (launch list)")
             return out
-    G = len(csr.groups_or_self(G_rule))
+    groups = csr.groups_or_self(G_rule)
+    G = len(groups)
     if G > 1:
         pl = None
-        parts = [(c, c.plan(0, n, threshold, hub_threshold, F)) for c in csr.column_groups(G)]
+        parts = [(c, c.plan(0, n, threshold, hub_threshold, F)) for c in groups]
     else:
         pl = csr.plan(0, n, threshold, hub_threshold, F) if use_plan else NO_PLAN
         parts = [(csr, pl)]
@@ -894,9 +942,10 @@ def propagate(csr: DeviceCSR, X: torch.Tensor, K: int, out=None, use_plan=True, 
             for c, cp, gflags in parts:  # column groups: 0 plain, 1.. accumulate
                 args = (_lib.ptr(c.row_ptr), _lib.ptr(c.col_idx), _lib.ptr(c.val), 0, n,
                         _lib.ptr(src), src.stride(0), _lib.ptr(dst), dst.stride(0), F,
-                        _lib.ptr(cp.rows), cp.n_heavy, cp.n_hub, cp.threshold, flags | gflags)
+                        _lib.ptr(cp.rows), cp.n_heavy, cp.n_hub, cp.threshold, flags | gflags,
+                        cp.n_nonempty)
                 ops.append(("spmm", args, slot(src), slot(dst)))
-                _lib.check(lib.sgc_spmm_csr_f32_ex(*args, stream), "spmm_csr_f32")
+                _lib.check(lib.sgc_spmm_csr_f32_ex2(*args, stream), "spmm_csr_f32")
             if hop_hook:
                 hop_hook("end", h)
             src, nxt = dst, nxt ^ 1
@@ -924,7 +973,7 @@ class LaunchList:
             if kind == "pad":
                 rc = lib.sgc_launch_list_add_pad_rows(self.handle, *args, s_src, s_dst)
             else:
-                rc = lib.sgc_launch_list_add_spmm(self.handle, *args, s_src, s_dst)
+                rc = lib.sgc_launch_list_add_spmm_ex2(self.handle, *args, s_src, s_dst)
             _lib.check(rc, "launch_list_add")
 
     def __del__(self):
