@@ -84,4 +84,38 @@ __device__ __forceinline__ void set_elem(typename Vec<V>::T &x, int i, float v) 
 template <>
 __device__ __forceinline__ void set_elem<1>(float &x, int, float v) { x = v; }
 
+// The same vectors at 4-byte alignment: gfx950 runs with unaligned access
+// enabled, so an access through this type is still one
+// global_{load,store}_dwordx{2,4} (a caller's [N, 602] rows are 2,408 B
+// apart: 8-B aligned at best).
+template <int V> struct VecU { typedef float __attribute__((ext_vector_type(V), aligned(4))) T; };
+template <> struct VecU<1> { typedef float T; };
+
+// Columns f .. f+V-1 of a row that ends at column F and is only 4-byte
+// aligned: one V-wide access when the lane's vector lies wholly below F, the
+// scalar bounds-checked form for the one lane that straddles F (columns at or
+// beyond F are never touched; load_upto leaves them +0.0f).
+template <int V>
+__device__ __forceinline__ typename Vec<V>::T load_upto(const float *row, int f, int F) {
+    typename Vec<V>::T x;
+    if (f + V <= F) {
+        x = *reinterpret_cast<const typename VecU<V>::T *>(row + f);
+    } else {
+#pragma unroll
+        for (int v = 0; v < V; ++v) set_elem<V>(x, v, f + v < F ? row[f + v] : 0.0f);
+    }
+    return x;
+}
+
+template <int V>
+__device__ __forceinline__ void store_upto(float *row, int f, int F, const typename Vec<V>::T &x) {
+    if (f + V <= F) {
+        *reinterpret_cast<typename VecU<V>::T *>(row + f) = x;
+    } else {
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+            if (f + v < F) row[f + v] = lane_elem<V>(x, v);
+    }
+}
+
 }  // namespace sgc

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "common.h"
+#include "lane_lines.h"
 #include "x16.h"
 
 namespace sgc {
@@ -245,7 +246,8 @@ __device__ __forceinline__ void hub_body(
     const int fl = lane & (HC - 1);  // feature within the chunk
     const int seg = lane / HC;       // which run of IN nonzeros (HC = 32: 0 or 1)
     const int f = c * HC + fl;
-    const uint32_t boff = (f < F ? (uint32_t)f : 0u) * (uint32_t)sizeof(XT);
+    // lanes beyond F gather column F - 1: a line the chunk's active lanes read
+    const uint32_t boff = (uint32_t)gather_col(f, F, 1) * (uint32_t)sizeof(XT);
     const char *Xb = reinterpret_cast<const char *>(X);
     const int64_t row_bytes = ldx * (int64_t)sizeof(XT);
     const int n_round = (k1 - k0 + Sh::kRound - 1) / Sh::kRound;

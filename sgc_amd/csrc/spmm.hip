@@ -1,5 +1,5 @@
 // spmm.hip -- CSR SpMM  Y = S[rows] . X  for gfx950 (MI355X), bit-exact with
-// the reference CPU path (torch.spmm at /root/reference/utils.py:95).
+// the reference CPU path (torch.spmm at the reference's utils.py:95).
 //
 // Numerical contract (pinned by tests/golden): every output
 // element is ONE sequential fp32 FMA chain over its row's nonzeros in CSR
@@ -27,10 +27,14 @@
 //   * U nonzeros are in flight per wave before their FMAs (U*C*V registers);
 //     TLP (up to 8 waves/SIMD) hides the rest of the HBM/MALL latency.
 //
-// Work items beyond F (ragged last chunk) load a valid address (feature 0)
-// and are never stored, so no exec-mask branches sit in the inner loop.
+// Lanes beyond F (ragged last chunk) still execute every gather -- no
+// exec-mask branches sit in the inner loop -- and are never stored.  They
+// gather the last valid vector of their instruction's segment (gather_col,
+// lane_lines.h): a 128-B line an active lane of the same instruction reads
+// anyway, so the ragged chunk touches no line the result does not need.
 #include "common.h"
 #include "hub.h"
+#include "lane_lines.h"
 
 #include <algorithm>
 #include <map>
@@ -72,7 +76,7 @@ __device__ __forceinline__ void row_chunks_pipe(const int *__restrict__ col,
     for (int c = 0; c < C; ++c) {
         const int f = (chunk0 + c) * (kWave * V) + lane * V;
         ok[c] = f < F;
-        boff[c] = ok[c] ? uint32_t(f) * 4u : 0u;
+        boff[c] = uint32_t(gather_col(f, F, V)) * 4u;  // idle lanes: lane_lines.h
     }
     VT acc[C];
 #pragma unroll
@@ -170,7 +174,7 @@ __device__ __forceinline__ void row_chunks_pipe2(const int *__restrict__ col,
     for (int c = 0; c < C; ++c) {
         const int f = (chunk0 + c) * (kWave * V) + lane * V;
         ok[c] = f < F;
-        boff[c] = ok[c] ? uint32_t(f) * 4u : 0u;
+        boff[c] = uint32_t(gather_col(f, F, V)) * 4u;  // idle lanes: lane_lines.h
     }
     VT acc[C];
 #pragma unroll
@@ -283,7 +287,7 @@ __device__ __forceinline__ void row_pairs_pipe(const int *__restrict__ col,
                                                const float *__restrict__ val, int k0, int k1,
                                                const float *__restrict__ X, int64_t ldx,
                                                float *__restrict__ yrow, int F, int f_lane,
-                                               bool lane_ok, bool vec_store, int lane,
+                                               int f_end, bool vec_store, int lane,
                                                bool accum) {
     typedef float f4 __attribute__((ext_vector_type(4)));
     constexpr int kPairs = kWave / (2 * U);  // steps per 64-nonzero block
@@ -291,25 +295,24 @@ __device__ __forceinline__ void row_pairs_pipe(const int *__restrict__ col,
     if (accum && k1 == k0) return;
     typedef float f2 __attribute__((ext_vector_type(2)));
     const bool hi = lane >= 32;
-    const uint32_t boff = lane_ok ? uint32_t(f_lane) * 4u : 0u;
+    // f_end: where the computed columns of this item stop (a multiple of 4)
+    const bool lane_ok = f_lane < f_end;
+    const uint32_t boff = uint32_t(gather_col(f_lane, f_end, 4)) * 4u;  // idle lanes: lane_lines.h
     f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
     f2 acc2 = {0.0f, 0.0f};           // TR: features fo, fo + 1
     const int fo = f_lane + (hi ? 2 : 0);
     if (accum && lane_ok) {
+        // !vec_store: a caller's rows (4-B aligned, nothing readable from
+        // column F on) -- still one access per lane (load_upto / store_upto)
         if constexpr (TR) {
-            if (vec_store) {
+            if (vec_store)
                 acc2 = *reinterpret_cast<const f2 *>(yrow + fo);
-            } else {
-#pragma unroll
-                for (int v = 0; v < 2; ++v)
-                    if (fo + v < F) acc2[v] = yrow[fo + v];
-            }
+            else
+                acc2 = load_upto<2>(yrow, fo, F);
         } else if (vec_store) {
             acc = *reinterpret_cast<const f4 *>(yrow + f_lane);
         } else {
-#pragma unroll
-            for (int v = 0; v < 4; ++v)
-                if (f_lane + v < F) acc[v] = yrow[f_lane + v];
+            acc = load_upto<4>(yrow, f_lane, F);
         }
     }
     if (k1 > k0) {
@@ -402,22 +405,16 @@ __device__ __forceinline__ void row_pairs_pipe(const int *__restrict__ col,
     }
     if constexpr (TR) {
         if (lane_ok) {
-            if (vec_store) {
+            if (vec_store)
                 *reinterpret_cast<f2 *>(yrow + fo) = acc2;
-            } else {
-#pragma unroll
-                for (int v = 0; v < 2; ++v)
-                    if (fo + v < F) yrow[fo + v] = acc2[v];
-            }
+            else
+                store_upto<2>(yrow, fo, F, acc2);
         }
     } else if (!hi && lane_ok) {
-        if (vec_store) {
+        if (vec_store)
             *reinterpret_cast<f4 *>(yrow + f_lane) = acc;
-        } else {
-#pragma unroll
-            for (int v = 0; v < 4; ++v)
-                if (f_lane + v < F) yrow[f_lane + v] = acc[v];
-        }
+        else
+            store_upto<4>(yrow, f_lane, F, acc);
     }
 }
 
@@ -448,25 +445,24 @@ __device__ __forceinline__ void row_quads_pipe(const int *__restrict__ col,
                                                const float *__restrict__ val, int k0, int k1,
                                                const float *__restrict__ X, int64_t ldx,
                                                float *__restrict__ yrow, int F, int f_lane,
-                                               bool lane_ok, bool vec_store, int lane,
+                                               int f_end, bool vec_store, int lane,
                                                bool accum) {
     using VT = typename Vec<V>::T;
     constexpr int kSteps = kWave / (4 * U);  // steps per 64-nonzero block
     static_assert(kWave % (4 * U) == 0 && kSteps % 2 == 0, "4U must divide 64 into an even count");
     if (accum && k1 == k0) return;
     const int g = lane >> 4;
-    const uint32_t boff = lane_ok ? uint32_t(f_lane) * 4u : 0u;
+    // f_end: where the computed columns stop (a multiple of 4, so of V)
+    const bool lane_ok = f_lane < f_end;
+    const uint32_t boff = uint32_t(gather_col(f_lane, f_end, V)) * 4u;  // idle lanes: lane_lines.h
     VT acc;
 #pragma unroll
     for (int v = 0; v < V; ++v) set_elem<V>(acc, v, 0.0f);
     if (accum && lane_ok) {
-        if (vec_store) {
+        if (vec_store)
             acc = *reinterpret_cast<const VT *>(yrow + f_lane);
-        } else {
-#pragma unroll
-            for (int v = 0; v < V; ++v)
-                if (f_lane + v < F) set_elem<V>(acc, v, yrow[f_lane + v]);
-        }
+        else
+            acc = load_upto<V>(yrow, f_lane, F);
     }
     if (k1 > k0) {
         const char *Xb = reinterpret_cast<const char *>(X);
@@ -545,13 +541,10 @@ __device__ __forceinline__ void row_quads_pipe(const int *__restrict__ col,
             if (base + i * 4 * U <= last) step(base, i, true);
     }
     if (g == 0 && lane_ok) {
-        if (vec_store) {
+        if (vec_store)
             *reinterpret_cast<VT *>(yrow + f_lane) = acc;
-        } else {
-#pragma unroll
-            for (int v = 0; v < V; ++v)
-                if (f_lane + v < F) yrow[f_lane + v] = lane_elem<V>(acc, v);
-        }
+        else
+            store_upto<V>(yrow, f_lane, F, acc);
     }
 }
 
@@ -575,15 +568,17 @@ __device__ __forceinline__ void row_quadsT_pipe(const int *__restrict__ col,
                                                 const float *__restrict__ val, int k0, int k1,
                                                 const float *__restrict__ X, int64_t ldx,
                                                 float *__restrict__ yrow, int F, int f_lane,
-                                                bool lane_ok, int lane, bool accum) {
+                                                int f_end, int lane, bool accum) {
     typedef float f4 __attribute__((ext_vector_type(4)));
     constexpr int kSteps = kWave / (4 * U);  // steps per 64-nonzero block
     static_assert(kWave % (4 * U) == 0 && kSteps % 2 == 0, "4U must divide 64 into an even count");
     if (accum && k1 == k0) return;
     const int g = lane >> 4;
     const int fo = f_lane + g;  // this lane's output feature
+    // f_end: where the computed columns stop (a multiple of 4)
+    const bool lane_ok = f_lane < f_end;
     const bool own = lane_ok && fo < F;
-    const uint32_t boff = lane_ok ? uint32_t(f_lane) * 4u : 0u;
+    const uint32_t boff = uint32_t(gather_col(f_lane, f_end, 4)) * 4u;  // idle lanes: lane_lines.h
     float acc = 0.0f;
     if (accum && own) acc = yrow[fo];
     if (k1 > k0) {
@@ -711,7 +706,7 @@ __global__ __launch_bounds__(256) void spmm_csr_kernel(
             if (heavy_pairs & 1) {  // the same 128-float sub-chunk, two nonzeros per load
                 const int f = sub * 128 + (lane & 31) * 4;
                 row_pairs_pipe<kPairsU, false>(col, val, k0, k1, X, ldx,
-                                               Y + (int64_t)(row - row_begin) * ldy, F, f, f < F,
+                                               Y + (int64_t)(row - row_begin) * ldy, F, f, F,
                                                true, lane, accum != 0);
                 return;
             }
@@ -806,6 +801,8 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(
     const int wave = __builtin_amdgcn_readfirstlane((int)(bx * (kBlock / kWave) + wl));
     const int slice = blockIdx.y;
     const int R = kWave / LR;  // rows per wave (uniform)
+    // where this slice's computed columns stop: lanes at or beyond it are idle
+    const int seg_end = min(F_load, (slice + 1) * (LR * V));
     const int n_heavy_items = n_heavy * n_sub;
     if (wave < n_heavy_items) {
         const int h = wave / n_sub;
@@ -814,28 +811,26 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(
         if constexpr (QV == 4) {  // 16 lanes x 16 B per nonzero, transposed chains
             const int f = slice * (LR * V) + (lane & 15) * 4;
             row_quadsT_pipe<kQuadsU, O32>(col, val, k0, k1, X, ldx,
-                                          Y + (int64_t)(row - row_begin) * ldy, F, f, f < F_load,
+                                          Y + (int64_t)(row - row_begin) * ldy, F, f, seg_end,
                                           lane, accum != 0);
             return;
         } else if constexpr (QV > 0) {  // 16 lanes per row: four nonzeros per load
             const int f = slice * (LR * V) + (lane & 15) * QV;
             row_quads_pipe<QV, kQuadsU, O32>(col, val, k0, k1, X, ldx,
                                              Y + (int64_t)(row - row_begin) * ldy, F, f,
-                                             f < F_load, vec_store != 0, lane, accum != 0);
+                                             seg_end, vec_store != 0, lane, accum != 0);
             return;
         }
         if (heavy_pairs & 1) {  // n_sub == 1: one item per (row, slice), two nonzeros per load
-            const int j = lane & 31;
-            const int f = slice * (LR * V) + j * V;
+            const int f = slice * (LR * V) + (lane & 31) * V;  // active below seg_end
             if (heavy_pairs & 16)
                 row_pairs_pipe<kPairsU, O32, true>(col, val, k0, k1, X, ldx,
                                                    Y + (int64_t)(row - row_begin) * ldy, F, f,
-                                                   j < LR && f < F_load, vec_store != 0, lane,
-                                                   accum != 0);
+                                                   seg_end, vec_store != 0, lane, accum != 0);
             else
                 row_pairs_pipe<kPairsU, O32>(col, val, k0, k1, X, ldx,
                                              Y + (int64_t)(row - row_begin) * ldy, F, f,
-                                             j < LR && f < F_load, vec_store != 0, lane, accum != 0);
+                                             seg_end, vec_store != 0, lane, accum != 0);
             return;
         }
         const int sub = slice * n_sub + (wave - h * n_sub);  // in units of 64*VH floats
@@ -872,15 +867,19 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(
     }
     // the wave runs to its longest row; up to its shortest every step is
     // unpredicated (rows in length order make the two close)
-    int n_max = 0, n_min = INT32_MAX;
+    int n_max = 0, n_min = INT32_MAX, k_max = 0;  // k_max: first nonzero of the longest row
     for (int s = 0; s < R; ++s) {
         const int ls = __builtin_amdgcn_readlane(len, s * LR);
+        const int ks = __builtin_amdgcn_readlane(k0, s * LR);
+        if (ls > n_max) k_max = ks;
         n_max = max(n_max, ls);
         n_min = min(n_min, ls);
     }
     const int f = slice * (LR * V) + l * V;
-    const bool ok = sub < R && f < F_load;
-    const uint32_t boff = ok ? uint32_t(f) * 4u : 0u;
+    const bool ok = sub < R && f < seg_end;
+    // idle lanes (beyond the ragged last slice, or the lanes past the wave's
+    // R rows, which alias row 0's lanes) stay on a line an active lane reads
+    const uint32_t boff = uint32_t(gather_col(f, seg_end, V)) * 4u;
     const int lds_row = (sub < R ? sub : 0) * LB;  // this lane's row block in LDS
     f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
     // accumulate: continue the chains an earlier column-block pass stored;
@@ -888,29 +887,29 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(
     const bool store = mine && ok && (!accum || len > 0);
     if (accum && store) {
         const float *yr = Y + (int64_t)r * ldy;
-        if (vec_store) {
+        if (vec_store)
             acc = *reinterpret_cast<const f4 *>(yr + f);
-        } else {
-#pragma unroll
-            for (int v = 0; v < V; ++v)
-                if (f + v < F) acc[v] = yr[f + v];
-        }
+        else  // a caller's rows: 4-B aligned, nothing readable from column F on
+            acc = load_upto<V>(yr, f, F);
     }
     if (n_max > 0) {
         const char *Xb = reinterpret_cast<const char *>(X);
         const int64_t row_bytes = ldx * 4;
         // lanes l < LB stage (col, val) of their row's nonzero base + l,
-        // clamped to its last one; a row without nonzeros reads X row 0 (its
-        // FMAs are all skipped)
+        // clamped to its last one; a row without nonzeros stages (and then
+        // gathers) what the wave's longest row does (its FMAs are all skipped)
         const bool stager = sub < R && l < LB;
         // Never predicated: a conditional load makes (c, v) a phi whose
         // default copy must wait for every load in flight (s_waitcnt
         // vmcnt(0) once per block: the gathers of the steps ahead drained
-        // at every LB nonzeros).  Lanes without a nonzero to stage read
-        // nonzero 0 (valid: n_max > 0 means the CSR has one); the value is
-        // either not staged or belongs to a row whose FMAs are all skipped.
+        // at every LB nonzeros).  Lanes without a nonzero to stage repeat the
+        // address of a lane that has one (stage_index, lane_lines.h): lanes
+        // l >= LB their row's lane LB - 1, lanes of an empty row or of no row
+        // the longest row's (n_max > 0: it has nonzeros); the value is either
+        // not staged or belongs to a row whose FMAs are all skipped.
+        const int k0_s = len > 0 ? k0 : k_max, len_s = len > 0 ? len : n_max;
         auto fetch = [&](int base, int &c, float &v) {
-            const int kk = (len > 0 && l < LB) ? k0 + min(base + l, len - 1) : 0;
+            const int kk = k0_s + stage_index(base, l, LB, len_s);
             c = col[kk];
             v = val[kk];
         };
@@ -989,13 +988,10 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(
     }
     if (store) {
         float *yr = Y + (int64_t)r * ldy;
-        if (vec_store) {
+        if (vec_store)
             *reinterpret_cast<f4 *>(yr + f) = acc;
-        } else {
-#pragma unroll
-            for (int v = 0; v < V; ++v)
-                if (f + v < F) yr[f + v] = acc[v];
-        }
+        else  // one 16-B store per lane; only the lane that straddles F goes scalar
+            store_upto<V>(yr, f, F, acc);
     }
 }
 
@@ -1811,6 +1807,9 @@ __global__ __launch_bounds__(256) void pad_rows_kernel(const float *__restrict__
     }
 }
 
+// (16-B lanes for 8-B aligned source rows -- unaligned dwordx4 loads, aligned
+// stores, a scalar tail -- measured no faster than V = 2 at Reddit shape:
+// 0.207 vs 0.205 ms, profiles/ragged_lines.)
 int launch_pad_rows(const float *src, int64_t lds, float *dst, int64_t ldd, int64_t n_rows,
                     int64_t F, hipStream_t stream) {
     SGC_REQUIRE(src && dst && lds >= F && ldd >= F && n_rows >= 0 && F >= 0 && F < INT32_MAX,

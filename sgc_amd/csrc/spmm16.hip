@@ -146,7 +146,7 @@ __device__ __forceinline__ void row16_pipe(const int *__restrict__ col,
     static_assert(kWave % U == 0 && kSteps % 2 == 0, "U must divide 64 into an even count");
     if (accum && k1 == k0) return;  // nothing to add: the row keeps its partial chains
     const bool ok = f < F;
-    const uint32_t boff = ok ? uint32_t(f) * 2u : 0u;
+    const uint32_t boff = uint32_t(gather_col(f, F, V)) * 2u;  // idle lanes: lane_lines.h
     float acc[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) acc[v] = 0.0f;
