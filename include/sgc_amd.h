@@ -86,7 +86,20 @@ const char *sgc_last_error(void);
  *                   column blocks up to 48 classes, else the fp32 MFMA
  *                   slabs), 1 = fp32 MFMA slabs, 2 = split-bf16 slabs where X
  *                   gives 8-B lanes (K and ldx even), 3 = split-bf16 column
- *                   blocks (up to 48 classes; more: as 0).
+ *                   blocks (up to 48 classes; more: as 0);
+ *   "short_wide":   wide items of the multi-row SpMM kernel: a light row of at
+ *                   most Ts nonzeros crosses every feature slice in one wave
+ *                   instead of one wave per slice (sgc_spmm_csr_f32_ex3).  -1
+ *                   (default) = the rule: Ts = 16 on launches of at least
+ *                   65,536 rows; 0 = off; 1..32 forces Ts on every launch that
+ *                   can take wide items (32 lanes per row, a light order, at
+ *                   least two slices, no fused hub rows).  Read-only beside
+ *                   it: "short_wide_ts" = the Ts in force (0 = off), which a
+ *                   caller of sgc_spmm_csr_f32_ex3 counts rows against, and
+ *                   "short_wide_launches" = launches that took wide items,
+ *                   "short_wide_state" = (knob + 1) * 64 + Ts in one read;
+ *   "short_wide_first": 1 = the wide waves' workgroups come first in the
+ *                   grid, 0 (default) = last.
  * sgc_get_tuning returns -1 for an unknown key. */
 int sgc_set_tuning(const char *key, int64_t value);
 int64_t sgc_get_tuning(const char *key);
@@ -305,6 +318,26 @@ int sgc_spmm_csr_f32_ex2(const int32_t *row_ptr, const int32_t *col_idx, const f
                          int32_t heavy_threshold, uint32_t flags, int64_t n_nonempty,
                          void *stream);
 
+/* sgc_spmm_csr_f32_ex2 with wide items: n_not_wide = the plan's light rows
+ * (rows of at most heavy_threshold nonzeros) with MORE than wide_max_nnz
+ * nonzeros, wide_max_nnz = sgc_get_tuning("short_wide_ts") in 1..32
+ * (sgc_plan_sorted_ex2 counts the rows above 4 / 8 / 16 / 32: n_not_wide =
+ * that count - n_heavy).  With SGC_SPMM_LIGHT_ORDER the sorted plan lists
+ * those rows first among the light ones; the light rows after them -- up to
+ * n_nonempty in an SGC_SPMM_ACCUMULATE launch, else to the end, the rows
+ * without nonzeros included (written as zeros) -- run as wide items where the
+ * "short_wide" knob and the launch allow: one wave carries two such rows
+ * through every feature slice and no per-slice wave is started for them.
+ * n_not_wide < 0 is sgc_spmm_csr_f32_ex2 exactly.  A schedule only: every
+ * (row, feature) FMA chain is unchanged, so are the results; a count that
+ * does not match the plan gives wrong values for the miscounted rows. */
+int sgc_spmm_csr_f32_ex3(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
+                         int64_t row_begin, int64_t row_end,
+                         const float *X, int64_t ldx, float *Y, int64_t ldy, int64_t F,
+                         const int32_t *plan, int64_t n_heavy, int64_t n_hub,
+                         int32_t heavy_threshold, uint32_t flags, int64_t n_nonempty,
+                         int64_t n_not_wide, int32_t wide_max_nnz, void *stream);
+
 /* K hops X_K = S^K X_0 over all n_rows rows (utils.py:92-97, the whole
  * sgc_precompute loop).  out (row stride ldo) receives X_K.  Intermediate
  * hops live in the workspace with 128-B aligned rows (ld = F rounded up to 32
@@ -340,6 +373,18 @@ int sgc_propagate_groups_f32(int32_t groups, const int32_t *row_ptrs, const int3
                              const int64_t *n_hub_host, const int32_t *thresholds_host,
                              const uint32_t *plan_flags_host, void *workspace,
                              int64_t workspace_bytes, void *stream);
+/* The same with, per group, the plan's rows with nonzeros (n_nonempty_host,
+ * sgc_spmm_csr_f32_ex2) and its light rows above wide_max_nnz nonzeros
+ * (n_not_wide_host, sgc_spmm_csr_f32_ex3); either may be NULL (= unknown). */
+int sgc_propagate_groups_f32_ex3(int32_t groups, const int32_t *row_ptrs, const int32_t *col_idx,
+                                 const float *val, int64_t n_rows, const float *X0, int64_t ldx,
+                                 float *out, int64_t ldo, int64_t F, int32_t K,
+                                 const int32_t *const *plans_host, const int64_t *n_heavy_host,
+                                 const int64_t *n_hub_host, const int32_t *thresholds_host,
+                                 const uint32_t *plan_flags_host,
+                                 const int64_t *n_nonempty_host, const int64_t *n_not_wide_host,
+                                 int32_t wide_max_nnz, void *workspace, int64_t workspace_bytes,
+                                 void *stream);
 
 /* Row-strided copy dst[i, 0:F] = src[i, 0:F] (re-layout of feature rows). */
 int sgc_pad_rows_f32(const float *src, int64_t lds, float *dst, int64_t ldd,
@@ -420,6 +465,15 @@ int sgc_launch_list_add_spmm_ex2(int64_t handle, const int32_t *row_ptr,
                                  int64_t ldy, int64_t F, const int32_t *plan, int64_t n_heavy,
                                  int64_t n_hub, int32_t heavy_threshold, uint32_t flags,
                                  int64_t n_nonempty, int32_t x_slot, int32_t y_slot);
+/* (records an sgc_spmm_csr_f32_ex3 launch: n_not_wide / wide_max_nnz as there;
+ * the "short_wide" knob is read when the list runs) */
+int sgc_launch_list_add_spmm_ex3(int64_t handle, const int32_t *row_ptr,
+                                 const int32_t *col_idx, const float *val, int64_t row_begin,
+                                 int64_t row_end, const float *X, int64_t ldx, float *Y,
+                                 int64_t ldy, int64_t F, const int32_t *plan, int64_t n_heavy,
+                                 int64_t n_hub, int32_t heavy_threshold, uint32_t flags,
+                                 int64_t n_nonempty, int64_t n_not_wide, int32_t wide_max_nnz,
+                                 int32_t x_slot, int32_t y_slot);
 int sgc_launch_list_add_pad_rows(int64_t handle, const float *src, int64_t lds, float *dst,
                                  int64_t ldd, int64_t n_rows, int64_t F, int32_t src_slot,
                                  int32_t dst_slot);
@@ -661,6 +715,16 @@ int sgc_plan_sorted(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
 int sgc_plan_sorted_ex(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
                        int32_t threshold, int32_t hub_threshold, int32_t *plan, void *workspace,
                        int64_t workspace_bytes, int64_t *counts_host, void *stream);
+/* The same with four more counts: counts_host[4..7] = rows of the range with
+ * more than 4 / 8 / 16 / 32 nonzeros (heavy rows among them).  Longest first,
+ * the non-empty rows of at most Ts nonzeros are the stretch just before the
+ * empty tail: a launch with wide items (sgc_spmm_csr_f32_ex3) takes
+ * n_not_wide = counts_host[4 + i] - n_heavy for Ts = 4 << i, so the
+ * "short_wide" knob moves without a new plan.  counts_host holds eight
+ * values here; the workspace is sgc_plan_sorted_workspace's. */
+int sgc_plan_sorted_ex2(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
+                        int32_t threshold, int32_t hub_threshold, int32_t *plan, void *workspace,
+                        int64_t workspace_bytes, int64_t *counts_host, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Column groups of S (a schedule for the SpMM of utils.py:95; results

@@ -48,11 +48,16 @@ SIGNATURES = {
                                            _p, _i64, _i64, _i32, _u32, _p]),
     "sgc_spmm_csr_f32_ex2": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _i64,
                                             _p, _i64, _i64, _i32, _u32, _i64, _p]),
+    "sgc_spmm_csr_f32_ex3": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _i64,
+                                            _p, _i64, _i64, _i32, _u32, _i64, _i64, _i32, _p]),
     "sgc_propagate_workspace": (_i64, [_i64, _i64, _i64, _i32]),
     "sgc_propagate_f32": (ctypes.c_int, [_p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i32,
                                          _p, _i64, _i64, _i32, _p, _i64, _p]),
     "sgc_propagate_groups_f32": (ctypes.c_int, [_i32, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i64,
                                                  _i32, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "sgc_propagate_groups_f32_ex3": (ctypes.c_int, [_i32, _p, _p, _p, _i64, _p, _i64, _p, _i64,
+                                                    _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _i32,
+                                                    _p, _i64, _p]),
     "sgc_pad_rows_f32": (ctypes.c_int, [_p, _i64, _p, _i64, _i64, _i64, _p]),
     "sgc_copy_blocks_f32": (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _p, _p]),
     "sgc_ipc_get_handle": (ctypes.c_int, [_p, _p]),
@@ -71,6 +76,9 @@ SIGNATURES = {
     "sgc_launch_list_add_spmm_ex2": (ctypes.c_int, [_i64, _p, _p, _p, _i64, _i64, _p, _i64, _p,
                                                     _i64, _i64, _p, _i64, _i64, _i32, _u32, _i64,
                                                     _i32, _i32]),
+    "sgc_launch_list_add_spmm_ex3": (ctypes.c_int, [_i64, _p, _p, _p, _i64, _i64, _p, _i64, _p,
+                                                    _i64, _i64, _p, _i64, _i64, _i32, _u32, _i64,
+                                                    _i64, _i32, _i32, _i32]),
     "sgc_launch_list_add_pad_rows": (ctypes.c_int, [_i64, _p, _i64, _p, _i64, _i64, _i64, _i32,
                                                     _i32]),
     "sgc_launch_list_run": (ctypes.c_int, [_i64, _p, _p, _p]),
@@ -106,6 +114,7 @@ SIGNATURES = {
     "sgc_plan_sorted_workspace": (_i64, [_i64]),
     "sgc_plan_sorted": (ctypes.c_int, [_p, _i64, _i64, _i32, _i32, _p, _p, _i64, _p, _p]),
     "sgc_plan_sorted_ex": (ctypes.c_int, [_p, _i64, _i64, _i32, _i32, _p, _p, _i64, _p, _p]),
+    "sgc_plan_sorted_ex2": (ctypes.c_int, [_p, _i64, _i64, _i32, _i32, _p, _p, _i64, _p, _p]),
     "sgc_mgpu_init": (ctypes.c_int, [ctypes.c_int, _p]),
     "sgc_mgpu_attach": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _p, ctypes.POINTER(_i64)]),
     "sgc_mgpu_propagate": (ctypes.c_int, [_i64, _p, _i64, _p, _i64, _i64, _i32, _p]),

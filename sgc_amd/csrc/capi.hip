@@ -35,7 +35,7 @@ int launch_spmm(const int32_t *row_ptr, const int32_t *col_idx, const float *val
                 int64_t row_begin, int64_t row_end, const float *X, int64_t ldx, float *Y,
                 int64_t ldy, int64_t F, const int32_t *heavy_rows, int64_t n_heavy,
                 int64_t n_hub, int32_t heavy_threshold, uint32_t flags, hipStream_t stream,
-                int64_t n_nonempty = -1);
+                int64_t n_nonempty = -1, int64_t n_not_wide = -1, int32_t wide_max_nnz = 0);
 int launch_spmm_x16(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
                     int64_t row_begin, int64_t row_end, const void *X, int32_t x_dtype,
                     int64_t ldx, void *Y, int32_t y_dtype, int64_t ldy, int64_t F,
@@ -113,6 +113,9 @@ int plan_sorted(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int3
 int plan_sorted_ex(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
                    int32_t hub_threshold, int32_t *plan, void *workspace,
                    int64_t workspace_bytes, int64_t *counts_host, hipStream_t stream);
+int plan_sorted_ex2(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
+                    int32_t hub_threshold, int32_t *plan, void *workspace,
+                    int64_t workspace_bytes, int64_t *counts_host, hipStream_t stream);
 int64_t colsplit_workspace(int64_t n_rows, int32_t groups);
 int colsplit(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n_rows,
              int64_t n_cols, int32_t groups, const int32_t *cuts_host, int32_t *row_ptrs,
@@ -278,6 +281,21 @@ int sgc_spmm_csr_f32_ex2(const int32_t *row_ptr, const int32_t *col_idx, const f
                        as_stream(stream), plan ? n_nonempty : -1);
 }
 
+int sgc_spmm_csr_f32_ex3(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
+                         int64_t row_begin, int64_t row_end, const float *X, int64_t ldx,
+                         float *Y, int64_t ldy, int64_t F, const int32_t *plan, int64_t n_heavy,
+                         int64_t n_hub, int32_t heavy_threshold, uint32_t flags,
+                         int64_t n_nonempty, int64_t n_not_wide, int32_t wide_max_nnz,
+                         void *stream) {
+    SGC_REQUIRE((flags & ~kSpmmFlags) == 0, SGC_EINVAL, "spmm_ex3: unknown flags 0x%x", flags);
+    SGC_REQUIRE(!((flags & SGC_SPMM_NO_HUB) && (flags & SGC_SPMM_HUB_ONLY)), SGC_EINVAL,
+                "spmm_ex3: NO_HUB and HUB_ONLY together");
+    return launch_spmm(row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F, plan,
+                       plan ? n_heavy : 0, plan ? n_hub : 0, heavy_threshold, flags,
+                       as_stream(stream), plan ? n_nonempty : -1, plan ? n_not_wide : -1,
+                       wide_max_nnz);
+}
+
 int sgc_spmm_csr_x16(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
                      int64_t row_begin, int64_t row_end, const void *X, int32_t x_dtype,
                      int64_t ldx, void *Y, int32_t y_dtype, int64_t ldy, int64_t F,
@@ -365,6 +383,8 @@ struct ListOp {
     uint32_t flags;
     int32_t x_slot, y_slot;  // SGC_SLOT_*: the pointer as recorded, or the run's X_0 / X_K
     int64_t n_nonempty = -1;  // the plan's rows with nonzeros (sgc_spmm_csr_f32_ex2), -1 unknown
+    int64_t n_not_wide = -1;  // its light rows above wide_max_nnz (sgc_spmm_csr_f32_ex3), -1 none
+    int32_t wide_max_nnz = 0;
 };
 
 struct LaunchList {
@@ -451,6 +471,25 @@ int sgc_launch_list_add_spmm_ex2(int64_t handle, const int32_t *row_ptr, const i
     return list_add(handle, op);
 }
 
+int sgc_launch_list_add_spmm_ex3(int64_t handle, const int32_t *row_ptr, const int32_t *col_idx,
+                                 const float *val, int64_t row_begin, int64_t row_end,
+                                 const float *X, int64_t ldx, float *Y, int64_t ldy, int64_t F,
+                                 const int32_t *plan, int64_t n_heavy, int64_t n_hub,
+                                 int32_t heavy_threshold, uint32_t flags, int64_t n_nonempty,
+                                 int64_t n_not_wide, int32_t wide_max_nnz, int32_t x_slot,
+                                 int32_t y_slot) {
+    SGC_REQUIRE((flags & ~kSpmmFlags) == 0, SGC_EINVAL,
+                "launch_list_add_spmm: unknown flags 0x%x", flags);
+    SGC_REQUIRE(!((flags & SGC_SPMM_NO_HUB) && (flags & SGC_SPMM_HUB_ONLY)), SGC_EINVAL,
+                "launch_list_add_spmm: NO_HUB and HUB_ONLY together");
+    ListOp op{0, row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F, plan,
+              plan ? n_heavy : 0, plan ? n_hub : 0, heavy_threshold, flags, x_slot, y_slot};
+    op.n_nonempty = plan ? n_nonempty : -1;
+    op.n_not_wide = plan ? n_not_wide : -1;
+    op.wide_max_nnz = wide_max_nnz;
+    return list_add(handle, op);
+}
+
 int sgc_launch_list_add_pad_rows(int64_t handle, const float *src, int64_t lds, float *dst,
                                  int64_t ldd, int64_t n_rows, int64_t F, int32_t src_slot,
                                  int32_t dst_slot) {
@@ -485,7 +524,8 @@ int sgc_launch_list_run(int64_t handle, const float *X0, float *out, void *strea
         }
         rc = op.kind == 0 ? launch_spmm(op.row_ptr, op.col_idx, op.val, op.row_begin, op.row_end, x,
                                         op.ldx, y, op.ldy, op.F, op.plan, op.n_heavy, op.n_hub,
-                                        op.threshold, op.flags, s, op.n_nonempty)
+                                        op.threshold, op.flags, s, op.n_nonempty, op.n_not_wide,
+                                        op.wide_max_nnz)
                           : launch_pad_rows(x, op.ldx, y, op.ldy, op.row_end, op.F, s);
         if (rc != SGC_OK) break;
     }
@@ -493,13 +533,15 @@ int sgc_launch_list_run(int64_t handle, const float *X0, float *out, void *strea
     return rc;
 }
 
-int sgc_propagate_groups_f32(int32_t groups, const int32_t *row_ptrs, const int32_t *col_idx,
-                             const float *val, int64_t n_rows, const float *X0, int64_t ldx,
-                             float *out, int64_t ldo, int64_t F, int32_t K,
-                             const int32_t *const *plans_host, const int64_t *n_heavy_host,
-                             const int64_t *n_hub_host, const int32_t *thresholds_host,
-                             const uint32_t *plan_flags_host, void *workspace,
-                             int64_t workspace_bytes, void *stream) {
+int sgc_propagate_groups_f32_ex3(int32_t groups, const int32_t *row_ptrs, const int32_t *col_idx,
+                                 const float *val, int64_t n_rows, const float *X0, int64_t ldx,
+                                 float *out, int64_t ldo, int64_t F, int32_t K,
+                                 const int32_t *const *plans_host, const int64_t *n_heavy_host,
+                                 const int64_t *n_hub_host, const int32_t *thresholds_host,
+                                 const uint32_t *plan_flags_host,
+                                 const int64_t *n_nonempty_host, const int64_t *n_not_wide_host,
+                                 int32_t wide_max_nnz, void *workspace, int64_t workspace_bytes,
+                                 void *stream) {
     hipStream_t s = as_stream(stream);
     SGC_REQUIRE(K >= 0, SGC_EINVAL, "propagate: negative degree %d", K);
     SGC_REQUIRE(groups >= 1 && groups <= 8, SGC_EINVAL, "propagate: groups must be 1..8");
@@ -550,7 +592,10 @@ int sgc_propagate_groups_f32(int32_t groups, const int32_t *row_ptrs, const int3
             const int rc = launch_spmm(row_ptrs + (int64_t)g * (n_rows + 1), col_idx, val, 0,
                                        n_rows, src, lds, dst, ldd, F, plan,
                                        plan ? n_heavy_host[g] : 0, plan ? n_hub_host[g] : 0,
-                                       plan ? thresholds_host[g] : 0, gf, s);
+                                       plan ? thresholds_host[g] : 0, gf, s,
+                                       plan && n_nonempty_host ? n_nonempty_host[g] : -1,
+                                       plan && n_not_wide_host ? n_not_wide_host[g] : -1,
+                                       wide_max_nnz);
             if (rc) return rc;
         }
         src = dst;
@@ -558,6 +603,19 @@ int sgc_propagate_groups_f32(int32_t groups, const int32_t *row_ptrs, const int3
         next ^= 1;
     }
     return SGC_OK;
+}
+
+int sgc_propagate_groups_f32(int32_t groups, const int32_t *row_ptrs, const int32_t *col_idx,
+                             const float *val, int64_t n_rows, const float *X0, int64_t ldx,
+                             float *out, int64_t ldo, int64_t F, int32_t K,
+                             const int32_t *const *plans_host, const int64_t *n_heavy_host,
+                             const int64_t *n_hub_host, const int32_t *thresholds_host,
+                             const uint32_t *plan_flags_host, void *workspace,
+                             int64_t workspace_bytes, void *stream) {
+    return sgc_propagate_groups_f32_ex3(groups, row_ptrs, col_idx, val, n_rows, X0, ldx, out, ldo,
+                                        F, K, plans_host, n_heavy_host, n_hub_host,
+                                        thresholds_host, plan_flags_host, nullptr, nullptr, 0,
+                                        workspace, workspace_bytes, stream);
 }
 
 int sgc_propagate_f32(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
@@ -772,6 +830,13 @@ int sgc_plan_sorted(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
                     int64_t workspace_bytes, int64_t *counts_host, void *stream) {
     return plan_sorted(row_ptr, row_begin, row_end, threshold, hub_threshold, plan, workspace,
                        workspace_bytes, counts_host, as_stream(stream));
+}
+
+int sgc_plan_sorted_ex2(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
+                        int32_t threshold, int32_t hub_threshold, int32_t *plan, void *workspace,
+                        int64_t workspace_bytes, int64_t *counts_host, void *stream) {
+    return plan_sorted_ex2(row_ptr, row_begin, row_end, threshold, hub_threshold, plan, workspace,
+                           workspace_bytes, counts_host, as_stream(stream));
 }
 
 int sgc_plan_sorted_ex(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,

@@ -41,7 +41,7 @@ int launch_spmm(const int32_t *row_ptr, const int32_t *col_idx, const float *val
                 int64_t row_begin, int64_t row_end, const float *X, int64_t ldx, float *Y,
                 int64_t ldy, int64_t F, const int32_t *heavy_rows, int64_t n_heavy,
                 int64_t n_hub, int32_t heavy_threshold, uint32_t flags, hipStream_t stream,
-                int64_t n_nonempty = -1);
+                int64_t n_nonempty = -1, int64_t n_not_wide = -1, int32_t wide_max_nnz = 0);
 int launch_pad_rows(const float *src, int64_t lds, float *dst, int64_t ldd, int64_t n_rows,
                     int64_t F, hipStream_t stream);
 int64_t colsplit_workspace(int64_t n_rows, int32_t groups);

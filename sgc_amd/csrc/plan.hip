@@ -22,6 +22,7 @@ __global__ void plan_keys_kernel(const int32_t *__restrict__ row_ptr, int row_be
                                  int threshold, int hub_threshold, uint32_t *__restrict__ deg,
                                  int32_t *__restrict__ ids, int32_t *__restrict__ counts) {
     int heavy = 0, hub = 0, top = 0, nonempty = 0;
+    int above[4] = {0, 0, 0, 0};  // rows of more than 4 / 8 / 16 / 32 nonzeros
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_rows;
          i += (int64_t)gridDim.x * blockDim.x) {
         const int row = row_begin + (int)i;
@@ -32,6 +33,8 @@ __global__ void plan_keys_kernel(const int32_t *__restrict__ row_ptr, int row_be
         hub += d > hub_threshold;
         nonempty += d > 0;
         top = max(top, d);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) above[t] += d > (4 << t);
     }
     // wave-level reduction, then one atomic per wave (vector atomics)
     for (int o = 32; o > 0; o >>= 1) {
@@ -39,31 +42,39 @@ __global__ void plan_keys_kernel(const int32_t *__restrict__ row_ptr, int row_be
         hub += __shfl_xor(hub, o);
         nonempty += __shfl_xor(nonempty, o);
         top = max(top, __shfl_xor(top, o));
+#pragma unroll
+        for (int t = 0; t < 4; ++t) above[t] += __shfl_xor(above[t], o);
     }
     if ((threadIdx.x & (kWave - 1)) == 0) {
         if (heavy) atomicAdd(&counts[0], heavy);
         if (hub) atomicAdd(&counts[1], hub);
         atomicMax(&counts[2], top);
         if (nonempty) atomicAdd(&counts[3], nonempty);
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            if (above[t]) atomicAdd(&counts[4 + t], above[t]);
     }
 }
 
 size_t sort_temp_bytes(int64_t n) { return (size_t)radix_sort_workspace(n); }
 
 constexpr size_t kAlign = 256;
+constexpr int kPlanCounts = 8;  // (one kAlign block, as the four counts were)
 size_t up(size_t b) { return (b + kAlign - 1) / kAlign * kAlign; }
 
 }  // namespace
 
 int64_t plan_sorted_workspace(int64_t n_rows) {
     if (n_rows <= 0) return (int64_t)kAlign;
-    return (int64_t)(up(4 * sizeof(int32_t)) + 3 * up((size_t)n_rows * sizeof(int32_t)) +
+    return (int64_t)(up(kPlanCounts * sizeof(int32_t)) + 3 * up((size_t)n_rows * sizeof(int32_t)) +
                      up(sort_temp_bytes(n_rows)));
 }
 
 // counts_host[0..3]: rows above threshold, rows above hub_threshold, the
-// longest row's nonzeros, rows with at least one nonzero
-int plan_sorted_ex(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
+// longest row's nonzeros, rows with at least one nonzero; [4..7]: rows of
+// more than 4 / 8 / 16 / 32 nonzeros (what a launch with wide items counts
+// its per-slice light rows from)
+int plan_sorted_ex2(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
                    int32_t hub_threshold, int32_t *plan, void *workspace,
                    int64_t workspace_bytes, int64_t *counts_host, hipStream_t stream) {
     SGC_REQUIRE(row_ptr && plan && counts_host && workspace, SGC_EINVAL, "plan_sorted: null pointer");
@@ -72,14 +83,14 @@ int plan_sorted_ex(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, i
     const int64_t n = row_end - row_begin;
     SGC_REQUIRE(n >= 0 && row_begin >= 0 && row_end < INT32_MAX, SGC_ERANGE,
                 "plan_sorted: bad row range");
-    counts_host[0] = counts_host[1] = counts_host[2] = counts_host[3] = 0;
+    for (int i = 0; i < kPlanCounts; ++i) counts_host[i] = 0;
     if (n == 0) return SGC_OK;
     SGC_REQUIRE(workspace_bytes >= plan_sorted_workspace(n), SGC_ENOMEM,
                 "plan_sorted: workspace %lld < %lld bytes", (long long)workspace_bytes,
                 (long long)plan_sorted_workspace(n));
     char *w = static_cast<char *>(workspace);
     int32_t *counts = reinterpret_cast<int32_t *>(w);
-    w += up(4 * sizeof(int32_t));
+    w += up(kPlanCounts * sizeof(int32_t));
     uint32_t *deg = reinterpret_cast<uint32_t *>(w);
     w += up((size_t)n * sizeof(int32_t));
     uint32_t *deg_sorted = reinterpret_cast<uint32_t *>(w);
@@ -87,18 +98,15 @@ int plan_sorted_ex(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, i
     int32_t *ids = reinterpret_cast<int32_t *>(w);
     w += up((size_t)n * sizeof(int32_t));
     size_t temp = sort_temp_bytes(n);
-    SGC_HIP_CHECK(hipMemsetAsync(counts, 0, 4 * sizeof(int32_t), stream));
+    SGC_HIP_CHECK(hipMemsetAsync(counts, 0, kPlanCounts * sizeof(int32_t), stream));
     const int blocks = (int)std::min<int64_t>((n + 255) / 256, 1024);
     hipLaunchKernelGGL(plan_keys_kernel, dim3(blocks), dim3(256), 0, stream, row_ptr,
                        (int)row_begin, (int)n, threshold, hub_threshold, deg, ids, counts);
     SGC_HIP_CHECK(hipGetLastError());
-    int32_t c[4] = {0, 0, 0, 0};
+    int32_t c[kPlanCounts] = {};
     SGC_HIP_CHECK(hipMemcpyAsync(c, counts, sizeof(c), hipMemcpyDeviceToHost, stream));
     SGC_HIP_CHECK(hipStreamSynchronize(stream));
-    counts_host[0] = c[0];
-    counts_host[1] = c[1];
-    counts_host[2] = c[2];
-    counts_host[3] = c[3];
+    for (int i = 0; i < kPlanCounts; ++i) counts_host[i] = c[i];
     // stable: equal degrees keep ascending row order; the longest row (read
     // back above) sets the passes.  Waited for, so the plan (and the
     // workspace) may be used from any stream once this returns.
@@ -107,6 +115,18 @@ int plan_sorted_ex(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, i
     if (rc != SGC_OK) return rc;
     SGC_HIP_CHECK(hipStreamSynchronize(stream));
     return SGC_OK;
+}
+
+// the four-count form
+int plan_sorted_ex(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
+                   int32_t hub_threshold, int32_t *plan, void *workspace,
+                   int64_t workspace_bytes, int64_t *counts_host, hipStream_t stream) {
+    SGC_REQUIRE(counts_host, SGC_EINVAL, "plan_sorted: null pointer");
+    int64_t c[kPlanCounts] = {};
+    const int rc = plan_sorted_ex2(row_ptr, row_begin, row_end, threshold, hub_threshold, plan,
+                                   workspace, workspace_bytes, c, stream);
+    for (int i = 0; i < 4; ++i) counts_host[i] = c[i];
+    return rc;
 }
 
 // the three-count form (heavy, hub, longest row)

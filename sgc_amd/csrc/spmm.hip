@@ -37,6 +37,7 @@
 #include "lane_lines.h"
 
 #include <algorithm>
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <string>
@@ -763,6 +764,166 @@ __global__ __launch_bounds__(256) void spmm_csr_kernel(
 constexpr int kRowsU = 4;  // nonzeros per row per step (one b128 (col, val) read each)
 
 
+// Wide item (short_wide): the wave's R = 2 light rows of at most LBW nonzeros,
+// carried through EVERY feature slice of the launch by this one wave.  The
+// per-slice path pays light_rows -> row_ptr -> (col, val) -> gathers -> FMAs
+// -> store once per slice and wave for rows that hold a handful of nonzeros;
+// here the first three are read once, the whole row sits in one LDS block
+// that is never restaged, and the (slice, step) pairs run as ONE software
+// pipeline: step t + 1 -- the next slice's first step when t ends a slice --
+// is issued before the FMAs of step t, so the gathers stay in flight across
+// the slice boundary.  Every (row, feature) chain is the per-slice path's:
+// fmaf in CSR order from +0.0f, or (ACC) from the stored value, loaded ahead
+// of the slice's first gathers.  Lane addressing as in the per-slice path:
+// gather_col against the current slice's seg_end, stage_index for the
+// staging lanes, stores into a caller's rows stop at F.  A row longer than
+// LBW (a caller's wrong count) is cut to LBW: wrong values, never a wild
+// address.
+template <int LBW, bool O32, bool ACC>
+__device__ __forceinline__ void wide_rows_body(
+    int ww, int wl, int lane, const int *__restrict__ row_ptr, const int *__restrict__ col,
+    const float *__restrict__ val, const float *__restrict__ X, int64_t ldx,
+    float *__restrict__ Y, int64_t ldy, int row_begin, int n_wide, int F, int F_load,
+    int vec_store, int n_slices, const int *__restrict__ wide_rows, int (*s_col)[2][kWave],
+    float (*s_val)[2][kWave]) {
+    constexpr int V = 4, U = 4, LR = 32, R = kWave / LR, SW = LR * V;
+    static_assert(R * LBW <= kWave && LBW % U == 0, "bad wide block");
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    typedef int i4 __attribute__((ext_vector_type(4)));
+    if (ww * R >= n_wide) return;  // wave-uniform
+    const int sub = lane / LR, l = lane - sub * LR;
+    const int li = ww * R + sub;
+    int r = 0, k0 = 0, len = 0;
+    bool mine = false;
+    if (li < n_wide) {
+        const int row = wide_rows[li];
+        r = row - row_begin;
+        k0 = row_ptr[row];
+        len = min(row_ptr[row + 1] - k0, LBW);
+        mine = true;
+    }
+    const int len0 = __builtin_amdgcn_readlane(len, 0), len1 = __builtin_amdgcn_readlane(len, LR);
+    const int n_max = max(len0, len1), n_min = min(len0, len1);
+    const int k_max = __builtin_amdgcn_readlane(k0, len1 > len0 ? LR : 0);
+    float *yr = Y + (int64_t)r * ldy;
+    // accumulate: rows without nonzeros in this pass are neither read into a
+    // result nor written
+    const bool live = mine && (!ACC || len > 0);
+    auto slice_end = [&](int s) { return min(F_load, (s + 1) * SW); };
+    auto store = [&](int s, const f4 &a) {
+        const int f = s * SW + l * V;
+        if (live && f < slice_end(s)) {
+            if (vec_store)
+                *reinterpret_cast<f4 *>(yr + f) = a;
+            else
+                store_upto<V>(yr, f, F, a);
+        }
+    };
+    if (n_max == 0) {  // only rows without nonzeros: zeros (a plain launch), or nothing
+        if constexpr (!ACC) {
+            const f4 z = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (int s = 0; s < n_slices; ++s) store(s, z);
+        }
+        return;
+    }
+    const char *Xb = reinterpret_cast<const char *>(X);
+    const int64_t row_bytes = ldx * 4;
+    const int lds_row = sub * LBW;
+    {   // the rows' (col, val), once: never predicated (stage_index, lane_lines.h);
+        // a row without nonzeros stages what the wave's longest row does
+        const int k0_s = len > 0 ? k0 : k_max, len_s = len > 0 ? len : n_max;
+        const int kk = k0_s + stage_index(0, l, LBW, len_s);
+        const int c = col[kk];
+        const float v = val[kk];
+        if (l < LBW) {
+            s_col[wl][0][lds_row + l] = c;
+            s_val[wl][0][lds_row + l] = v;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    const int nst = (n_max + U - 1) / U;  // steps per slice (wave-uniform)
+    const int T = nst * n_slices;
+    // idle lanes of a ragged slice stay on a line an active lane reads
+    auto slice_col = [&](int s) { return gather_col(s * SW + l * V, slice_end(s), V); };
+    f4 xv[2][U];
+    f4 acc = {0.0f, 0.0f, 0.0f, 0.0f}, accN = {0.0f, 0.0f, 0.0f, 0.0f};
+    int is = 0, ii = 0;  // the issue cursor: (slice, step)
+    int col_i = slice_col(0);
+    auto issue = [&](int slot) {
+        if constexpr (ACC) {
+            if (ii == 0) {  // uniform: the slice's stored chains, ahead of its gathers
+                // every lane loads (idle lanes their clamped column, lanes
+                // without a row the range's first row): nothing predicated
+                if (vec_store)
+                    accN = *reinterpret_cast<const f4 *>(yr + col_i);
+                else  // a caller's rows: nothing readable from column F on
+                    accN = load_upto<V>(yr, col_i, F);
+            }
+        }
+        const uint32_t boff = uint32_t(col_i) * 4u;
+        const i4 cc = *reinterpret_cast<const i4 *>(&s_col[wl][0][lds_row + ii * U]);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if constexpr (O32)
+                xv[slot][u] = *reinterpret_cast<const f4 *>(
+                    Xb + (__umul24((uint32_t)cc[u], (uint32_t)row_bytes) + boff));
+            else
+                xv[slot][u] = *reinterpret_cast<const f4 *>(Xb + (int64_t)cc[u] * row_bytes + boff);
+        }
+        if (++ii == nst) {  // uniform
+            ii = 0;
+            ++is;
+            col_i = slice_col(min(is, n_slices - 1));
+        }
+    };
+    int fs = 0, fi = 0;  // the FMA cursor: (slice, step)
+    // the step's S values come from LDS when its FMAs run (the block is never
+    // restaged), read ahead of the next step's gathers: four registers, not
+    // four per step in flight
+    auto vals = [&]() { return *reinterpret_cast<const f4 *>(&s_val[wl][0][lds_row + fi * U]); };
+    auto fma = [&](int slot, const f4 &vq) {
+        const int cur = fi * U;
+        if (cur + U <= n_min) {  // both rows have these U (uniform)
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int v = 0; v < V; ++v)
+                    acc[v] = __builtin_fmaf(vq[u], xv[slot][u][v], acc[v]);
+        } else {  // a row ends inside this step: per-lane predication
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (cur + u < len) {
+#pragma unroll
+                    for (int v = 0; v < V; ++v)
+                        acc[v] = __builtin_fmaf(vq[u], xv[slot][u][v], acc[v]);
+                }
+            }
+        }
+        if (++fi == nst) {  // uniform: the slice is complete
+            store(fs, acc);
+            fi = 0;
+            ++fs;
+            if constexpr (ACC)
+                acc = accN;
+            else
+                acc = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+    };
+    issue(0);
+    if constexpr (ACC) acc = accN;
+    for (int t = 0; t < T; t += 2) {  // steps t (slot 0) and t + 1 (slot 1)
+        const f4 v0 = vals();
+        if (t + 1 < T) issue(1);
+        fma(0, v0);
+        if (t + 1 >= T) break;
+        const f4 v1 = vals();
+        if (t + 2 < T) issue(0);
+        fma(1, v1);
+    }
+}
+
 // HF > 0: the fused rows + hub launch (small graphs whose hub chains are
 // short, SGC_SPMM_HUB_SERIAL): the first n_hub_blocks workgroups of slice 0
 // each run one (hub row, HF-float chunk) item of the hub kernel with three
@@ -771,14 +932,23 @@ constexpr int kRowsU = 4;  // nonzeros per row per step (one b128 (col, val) rea
 // the hub chains run beside the light rows with no second launch and no
 // cross-stream fork / join (Pubmed shape: the serial hub kernel added its
 // whole 15 us chain to every hop).
-template <int LB, int VH, int UH, bool O32, int QV, int HF = 0>
+//
+// WD > 0: the launch with wide items (wide_rows_body, LBW = WD; LR = 32, a
+// light order, at least two slices).  Its grid is one-dimensional: the
+// slice_blocks workgroups of each of the n_slices slices in turn -- the same
+// x-fastest sweep as the two-dimensional grid's -- and wide_blocks workgroups
+// of wide waves before them (wide_first) or after.  The per-slice light items
+// are the n_rows light rows above the wide threshold; light_rows[n_rows ..
+// n_rows + n_wide) are the wide rows, and no per-slice wave exists for them.
+template <int LB, int VH, int UH, bool O32, int QV, int HF = 0, int WD = 0>
 __global__ __launch_bounds__(256) void spmm_rows_kernel(
     const int *__restrict__ row_ptr, const int *__restrict__ col, const float *__restrict__ val,
     const float *__restrict__ X, int64_t ldx, float *__restrict__ Y, int64_t ldy,
     int row_begin, int n_rows, int F, int F_load, int LR, int vec_store, int n_sub,
     const int *__restrict__ heavy_rows, int n_heavy, int heavy_threshold, int accum,
     const int *__restrict__ light_rows, int heavy_pairs, const int *__restrict__ hub_rows = nullptr,
-    int hub_chunks = 0, int n_hub_blocks = 0) {
+    int hub_chunks = 0, int n_hub_blocks = 0, int n_wide = 0, int wide_blocks = 0,
+    int slice_blocks = 0, int n_slices = 0, int wide_first = 0) {
     int bx = (int)blockIdx.x;
     if constexpr (HF > 0) {
         if (bx < n_hub_blocks) {  // block-uniform
@@ -798,8 +968,33 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(
     __shared__ __attribute__((aligned(16))) float s_val[kBlock / kWave][2][kWave];
     const int lane = threadIdx.x & (kWave - 1);
     const int wl = threadIdx.x / kWave;
+    int wd_slice = 0;  // WD > 0: this workgroup's slice in the one-dimensional grid
+    if constexpr (WD > 0) {
+        static_assert(HF == 0 && QV == 0, "wide items: the plain multi-row launch only");
+        int wb = -1;  // block-uniform: this workgroup's index among the wide ones, or -1
+        if (wide_first) {
+            if (bx < wide_blocks) wb = bx;
+            bx -= wide_blocks;
+        } else if (bx >= slice_blocks * n_slices) {
+            wb = bx - slice_blocks * n_slices;
+        }
+        if (wb >= 0) {
+            const int ww = __builtin_amdgcn_readfirstlane(wb * (kBlock / kWave) + wl);
+            if (accum)
+                wide_rows_body<WD, O32, true>(ww, wl, lane, row_ptr, col, val, X, ldx, Y, ldy,
+                                              row_begin, n_wide, F, F_load, vec_store, n_slices,
+                                              light_rows + n_rows, s_col, s_val);
+            else
+                wide_rows_body<WD, O32, false>(ww, wl, lane, row_ptr, col, val, X, ldx, Y, ldy,
+                                               row_begin, n_wide, F, F_load, vec_store, n_slices,
+                                               light_rows + n_rows, s_col, s_val);
+            return;
+        }
+        wd_slice = bx / slice_blocks;  // (slice_blocks > 0: a per-slice block exists)
+        bx -= wd_slice * slice_blocks;
+    }
     const int wave = __builtin_amdgcn_readfirstlane((int)(bx * (kBlock / kWave) + wl));
-    const int slice = blockIdx.y;
+    const int slice = WD > 0 ? wd_slice : (int)blockIdx.y;
     const int R = kWave / LR;  // rows per wave (uniform)
     // where this slice's computed columns stop: lanes at or beyond it are idle
     const int seg_end = min(F_load, (slice + 1) * (LR * V));
@@ -1027,6 +1222,9 @@ struct LaunchArgs {
     // fused rows + hub launch (spmm_rows_kernel HF = 32): the hub rows and items
     const int *hub_rows = nullptr;
     int hub_chunks = 0, n_hub_blocks = 0;
+    // wide items (spmm_rows_kernel WD > 0): the last n_wide of the n_light
+    // light items run as wide waves; wide_first: before the slices' workgroups
+    int n_wide = 0, wide_first = 0;
 };
 
 // A side stream + fork/join events per (device, caller's stream) for the
@@ -1272,6 +1470,32 @@ hipError_t launch_rows(const LaunchArgs &a, int F_load, int LR, int vec_store) {
     return hipGetLastError();
 }
 
+// The launch with wide items (spmm_rows_kernel WD > 0; LR = 32, a light
+// order, at least two slices): a one-dimensional grid of the slices'
+// workgroups in turn plus the wide waves' workgroups, which replace the
+// per-slice waves of the last a.n_wide light items.
+template <int VH, bool O32, int WD>
+hipError_t launch_rows_wide(const LaunchArgs &a, int F_load, int vec_store) {
+    constexpr int LR = 32, R = kWave / LR, SW = LR * 4;
+    const int slices = (F_load + SW - 1) / SW;
+    const int n_sub = (g_heavy_pairs & 1) ? 1 : SW / (kWave * VH);
+    const int n_narrow = a.n_light - a.n_wide;
+    const int64_t waves = (int64_t)a.n_heavy * n_sub + (n_narrow + R - 1) / R;
+    const int64_t slice_blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
+    const int64_t wide_waves = (a.n_wide + R - 1) / R;
+    const int64_t wide_blocks = (wide_waves + kWavesPerBlock - 1) / kWavesPerBlock;
+    const int64_t blocks = slice_blocks * slices + wide_blocks;
+    if (blocks >= INT32_MAX || n_narrow < 0 || !a.light_rows) return hipErrorInvalidValue;
+    if (blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL((spmm_rows_kernel<16, VH, kHeavyU, O32, 0, 0, WD>), dim3((unsigned)blocks),
+                       dim3(kBlock), 0, a.stream, a.row_ptr, a.col, a.val, a.X, a.ldx, a.Y, a.ldy,
+                       a.row_begin, n_narrow, a.F, F_load, LR, vec_store, n_sub, a.heavy_rows,
+                       a.n_heavy, a.heavy_threshold, a.accum, a.light_rows, g_heavy_pairs & 17,
+                       nullptr, 0, 0, a.n_wide, (int)wide_blocks, (int)slice_blocks, slices,
+                       a.wide_first);
+    return hipGetLastError();
+}
+
 // Largest per-lane register vector the strides and base pointers allow.
 int pick_vec(int64_t F, int64_t ldx, int64_t ldy, const void *X, const void *Y) {
     for (int V : {4, 2}) {
@@ -1352,6 +1576,21 @@ static int g_hub_loaders = 15;
 // 16-B-lane slices or the one-chunk csr kernel.  Set through
 // sgc_set_tuning("hub_fuse").
 static int g_hub_fuse = 1;
+// Wide items (wide_rows_body): light rows of at most Ts nonzeros cross every
+// feature slice in one wave instead of one wave per slice.  0 = off; -1 = the
+// rule (Ts = kShortWideTs on launches of at least kWideRowsMin rows); 1..32
+// forces Ts on every launch that can take them (the multi-row kernel at 32
+// lanes per row, a light order, at least two slices, no fused hub rows).  The
+// caller passes the count of light rows above Ts with Ts itself (the plan
+// counts them for 4 / 8 / 16 / 32), so the knob moves without re-planning;
+// "short_wide_ts" reports the Ts in force (0 = off).  Set through
+// sgc_set_tuning("short_wide").
+static int g_short_wide = -1;
+constexpr int kShortWideTs = 16;
+// the wide waves' workgroups before (1) or after (0) the slices' in the grid
+static int g_short_wide_first = 0;
+// launches that took wide items since the library was loaded (diagnostics)
+static std::atomic<int64_t> g_short_wide_launches{0};
 
 extern int g_x16_vec, g_x16_step;  // spmm16.hip
 
@@ -1431,11 +1670,25 @@ int set_tuning(const char *key, int64_t value) {
         g_max_vec = (int)value;
         return SGC_OK;
     }
+    if (std::string(key) == "short_wide") {
+        SGC_REQUIRE(value >= -1 && value <= 32, SGC_EINVAL,
+                    "short_wide must be -1 (the rule), 0 (off) or 1..32");
+        g_short_wide = (int)value;
+        return SGC_OK;
+    }
+    if (std::string(key) == "short_wide_first") {
+        SGC_REQUIRE(value == 0 || value == 1, SGC_EINVAL, "short_wide_first must be 0 or 1");
+        g_short_wide_first = (int)value;
+        return SGC_OK;
+    }
     set_error("set_tuning: unknown key '%s'", key);
     return SGC_EINVAL;
 }
 
 int64_t get_tuning(const char *key) {
+    // (first: the Python layer reads it once per propagate() call)
+    if (key && std::string(key) == "short_wide_state")
+        return (int64_t)(g_short_wide + 1) * 64 + (g_short_wide < 0 ? kShortWideTs : g_short_wide);
     if (key && std::string(key) == "slice_floats") return g_slice_floats;
     if (key && std::string(key) == "max_vec") return g_max_vec;
     if (key && std::string(key) == "heavy_pairs") return g_heavy_pairs;
@@ -1450,6 +1703,11 @@ int64_t get_tuning(const char *key) {
     if (key && std::string(key) == "linear_kernel") return g_linear_kernel;
     if (key && std::string(key) == "linear_ck") return g_linear_ck;
     if (key && std::string(key) == "backward_kernel") return g_backward_kernel;
+    if (key && std::string(key) == "short_wide") return g_short_wide;
+    if (key && std::string(key) == "short_wide_ts")
+        return g_short_wide < 0 ? kShortWideTs : g_short_wide;
+    if (key && std::string(key) == "short_wide_first") return g_short_wide_first;
+    if (key && std::string(key) == "short_wide_launches") return g_short_wide_launches.load();
     return -1;
 }
 
@@ -1457,7 +1715,7 @@ int launch_spmm(const int32_t *row_ptr, const int32_t *col_idx, const float *val
                 int64_t row_begin, int64_t row_end, const float *X, int64_t ldx, float *Y,
                 int64_t ldy, int64_t F, const int32_t *heavy_rows, int64_t n_heavy,
                 int64_t n_hub, int32_t heavy_threshold, uint32_t flags, hipStream_t stream,
-                int64_t n_nonempty) {
+                int64_t n_nonempty, int64_t n_not_wide, int32_t wide_max_nnz) {
     // col_idx / val may be NULL for a CSR without nonzeros (torch's empty
     // tensors have no storage): the kernels never dereference them then
     SGC_REQUIRE(row_ptr && X && Y, SGC_EINVAL, "spmm: null pointer");
@@ -1489,6 +1747,19 @@ int launch_spmm(const int32_t *row_ptr, const int32_t *col_idx, const float *val
         SGC_REQUIRE(n_nonempty >= n_heavy && n_nonempty <= n_rows, SGC_EINVAL,
                     "spmm: n_nonempty %lld outside [n_heavy, rows]", (long long)n_nonempty);
         n_light = n_nonempty - n_heavy;
+    }
+    // Wide items: the caller's count of light rows with more than
+    // wide_max_nnz nonzeros (n_not_wide >= 0; the sorted plan lists them
+    // first) leaves the rest of the light items -- in a plain launch the
+    // rows without nonzeros too, written as zeros by the wide waves -- to
+    // wide waves, where the launch can take them (below).
+    int64_t n_wide = 0;
+    if (light_rows && n_not_wide >= 0 && g_short_wide != 0) {
+        SGC_REQUIRE(wide_max_nnz >= 1 && wide_max_nnz <= 32, SGC_EINVAL,
+                    "spmm: wide_max_nnz %d outside [1, 32]", wide_max_nnz);
+        SGC_REQUIRE(n_not_wide <= n_rows - n_heavy, SGC_EINVAL,
+                    "spmm: n_not_wide %lld > light rows", (long long)n_not_wide);
+        n_wide = std::max<int64_t>(0, n_light - n_not_wide);
     }
     if (!heavy_rows) {
         n_heavy = 0;
@@ -1673,7 +1944,22 @@ int launch_spmm(const int32_t *row_ptr, const int32_t *col_idx, const float *val
         int qv = ((g_heavy_pairs & 4) && LR <= 16 && F4 <= 32) ? (F4 > 16 ? 2 : 1) : 0;
         // 33..64 floats: the transposed quads (row_quadsT_pipe, heavy_pairs bit 8)
         if ((g_heavy_pairs & 8) && LR <= 16 && F4 > 32 && F4 <= 64) qv = 4;
-        if (qv == 4)  // the light rows' LDS block: LB * rows per wave <= 64
+        // wide items: 32 lanes per row over at least two slices, no fused
+        // hub rows; the rule asks for a large launch, a forced Ts does not
+        const bool wide = n_wide > 0 && LR == 32 && multi && !fused && qv == 0 &&
+                          (g_short_wide > 0 || n_rows >= kWideRowsMin);
+        if (wide) {
+            a.n_wide = (int)n_wide;
+            a.wide_first = g_short_wide_first;
+            g_short_wide_launches.fetch_add(1, std::memory_order_relaxed);
+#define SGC_WIDE(WDV)                                                                       \
+    (vh2 ? (o32 ? launch_rows_wide<2, true, WDV>(a, (int)F4, vec_store)                     \
+                : launch_rows_wide<2, false, WDV>(a, (int)F4, vec_store))                   \
+         : (o32 ? launch_rows_wide<1, true, WDV>(a, (int)F4, vec_store)                     \
+                : launch_rows_wide<1, false, WDV>(a, (int)F4, vec_store)))
+            e = wide_max_nnz <= 16 ? SGC_WIDE(16) : SGC_WIDE(32);
+#undef SGC_WIDE
+        } else if (qv == 4)  // the light rows' LDS block: LB * rows per wave <= 64
             e = LR >= 16 ? SGC_ROWS(16, 2, 4) : SGC_ROWS(8, 2, 4);
         else if (qv == 2)
             e = SGC_ROWS(8, 2, 2);

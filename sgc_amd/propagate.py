@@ -64,6 +64,7 @@ class Plan(NamedTuple):
     max_hub_degree: int = 0  # nonzeros of the longest hub row (0: no hub rows)
     ordered: bool = False  # rows also lists the light rows, longest first (SPMM_LIGHT_ORDER)
     n_nonempty: int = -1  # rows with at least one nonzero (sgc_plan_sorted_ex); -1: not counted
+    above: tuple = ()  # rows of more than 4 / 8 / 16 / 32 nonzeros (sgc_plan_sorted_ex2), heavy too
 
     @property
     def accumulate_light_items(self):
@@ -83,6 +84,39 @@ class Plan(NamedTuple):
 
 
 NO_PLAN = Plan(None, 0, 0, 0)
+
+# Wide items (sgc_spmm_csr_f32_ex3, the "short_wide" knob of sgc_set_tuning): a
+# light row of at most Ts nonzeros crosses every feature slice in one wave.
+# The plan counts the rows above each candidate Ts, so the knob moves without
+# a new plan; another forced Ts is counted from row_ptr once and cached.
+SHORT_WIDE_CANDIDATES = (4, 8, 16, 32)
+
+
+def short_wide_state():
+    """(knob, Ts in force) of the wide items: sgc_get_tuning "short_wide" (-1 the
+    rule, 0 off, 1..32 forced) and "short_wide_ts" (0 = off)."""
+    state = int(_lib.load().sgc_get_tuning(b"short_wide_state"))  # (knob + 1) * 64 + Ts: one call
+    return (state >> 6) - 1, state & 63
+
+
+def wide_args(csr, pl, row_begin, row_end, ts=None):
+    """(n_not_wide, wide_max_nnz) of sgc_spmm_csr_f32_ex3 for plan `pl` over rows
+    [row_begin, row_end) of `csr` at the Ts in force (or `ts`): the plan's light
+    rows with more than Ts nonzeros.  (-1, 0) -- no wide items -- when the
+    knob is off or the plan is not the sorted one."""
+    if ts is None:
+        ts = short_wide_state()[1]
+    if ts <= 0 or not pl.ordered or pl.n_nonempty < 0 or len(pl.above) != 4:
+        return -1, 0
+    if ts in SHORT_WIDE_CANDIDATES:
+        above = pl.above[SHORT_WIDE_CANDIDATES.index(ts)]
+    else:
+        key = ("above", row_begin, row_end, ts)
+        if key not in csr._plans:
+            rp = csr.row_ptr[row_begin:row_end + 1]
+            csr._plans[key] = int(((rp[1:] - rp[:-1]) > ts).sum().item())
+        above = csr._plans[key]
+    return max(0, above - pl.n_heavy), int(ts)
 
 SLOT_FIXED, SLOT_X0, SLOT_OUT = 0, 1, 2  # sgc_launch_list_* pointer slots
 SPMM_X_PADDED = 1  # sgc_spmm_csr_f32_ex flags (include/sgc_amd.h)
@@ -478,15 +512,15 @@ class DeviceCSR:
         rows = torch.empty(max(1, n), dtype=torch.int32, device=self.device)
         ws_bytes = lib.sgc_plan_sorted_workspace(n)
         ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=self.device)
-        counts = (ctypes.c_int64 * 4)()
+        counts = (ctypes.c_int64 * 8)()
         with torch.cuda.device(self.device):
-            _lib.check(lib.sgc_plan_sorted_ex(_lib.ptr(self.row_ptr), row_begin, row_end,
-                                              threshold, hub, _lib.ptr(rows), _lib.ptr(ws),
-                                              ws_bytes, ctypes.cast(counts, ctypes.c_void_p),
-                                              _lib.stream_handle(self.device)), "plan_sorted")
+            _lib.check(lib.sgc_plan_sorted_ex2(_lib.ptr(self.row_ptr), row_begin, row_end,
+                                               threshold, hub, _lib.ptr(rows), _lib.ptr(ws),
+                                               ws_bytes, ctypes.cast(counts, ctypes.c_void_p),
+                                               _lib.stream_handle(self.device)), "plan_sorted")
         h, nh = int(counts[0]), int(counts[1])
         return Plan(rows, h, nh, threshold, int(counts[2]) if nh > 0 else 0, n > h,
-                    int(counts[3]))
+                    int(counts[3]), tuple(int(c) for c in counts[4:8]))
 
 
 def to_torch_coo(csr: DeviceCSR):
@@ -747,13 +781,14 @@ def spmm(csr: DeviceCSR, X: torch.Tensor, row_begin=0, row_end=None, out=None,
         stream = _lib.stream_handle(X.device)
         for g, c in enumerate(parts):  # group 0 plain, groups 1.. continue its chains
             pl = c.plan(row_begin, row_end, threshold, hub_threshold, F) if use_plan else NO_PLAN
-            _lib.check(lib.sgc_spmm_csr_f32_ex2(_lib.ptr(c.row_ptr), _lib.ptr(c.col_idx),
+            _lib.check(lib.sgc_spmm_csr_f32_ex3(_lib.ptr(c.row_ptr), _lib.ptr(c.col_idx),
                                                 _lib.ptr(c.val), row_begin, row_end, _lib.ptr(X),
                                                 X.stride(0), _lib.ptr(out), out.stride(0), F,
                                                 _lib.ptr(pl.rows), pl.n_heavy, pl.n_hub,
                                                 pl.threshold,
                                                 int(flags) | pl.hub_flags() | x_flags(X) |
                                                 (SPMM_ACCUMULATE if g else 0), pl.n_nonempty,
+                                                *wide_args(c, pl, row_begin, row_end),
                                                 stream), "spmm_csr_f32")
     return out
 
@@ -780,12 +815,13 @@ class SpmmLaunch:
         F = X.shape[1]
         pl = csr.plan(row_begin, row_end, threshold, hub_threshold, F)
         lib = _lib.load()
-        self._fn = lib.sgc_spmm_csr_f32_ex2
+        self._fn = lib.sgc_spmm_csr_f32_ex3
         self._keep = (csr, X, out, pl) if keep_tensors else (csr, pl)
         self._args = (_lib.ptr(csr.row_ptr), _lib.ptr(csr.col_idx), _lib.ptr(csr.val),
                       int(row_begin), int(row_end), _lib.ptr(X), X.stride(0), _lib.ptr(out),
                       out.stride(0), F, _lib.ptr(pl.rows), pl.n_heavy, pl.n_hub, pl.threshold,
-                      int(flags) | pl.hub_flags() | x_flags(X), pl.n_nonempty)
+                      int(flags) | pl.hub_flags() | x_flags(X), pl.n_nonempty,
+                      *wide_args(csr, pl, int(row_begin), int(row_end)))
 
     def __call__(self, stream_handle):
         rc = self._fn(*self._args, stream_handle)
@@ -864,6 +900,7 @@ def propagate(csr: DeviceCSR, X: torch.Tensor, K: int, out=None, use_plan=True, 
         return out
     stream = torch.cuda.current_stream(X.device).cuda_stream  # (an int: ctypes takes it as void *)
     G_rule = column_groups_for(csr, F) if use_plan else 1
+    wide_knob, wide_ts = short_wide_state()
     # small launches (Cora / Pubmed shape: 20-40 us hops) pay their host time:
     # the loop's launches are recorded once per (shape, strides, X_0's 128-B
     # alignment, K, stream, schedule) into a native launch list, with the
@@ -874,7 +911,7 @@ def propagate(csr: DeviceCSR, X: torch.Tensor, K: int, out=None, use_plan=True, 
             and not torch.cuda.is_current_stream_capturing()):
         key = ("list", X.stride(0), F, int(K), out.stride(0), X.data_ptr() % 128 == 0,
                threshold, hub_threshold, bool(use_plan), G_rule,
-               group_whole_rows_for(csr, G_rule), stream, PAD_X0)
+               group_whole_rows_for(csr, G_rule), stream, PAD_X0, wide_knob, wide_ts)
         prep = csr._plans.get(key)
         if prep is not None:
             rc = lib.sgc_launch_list_run(prep[1].handle, X.data_ptr(), out.data_ptr(), stream)
@@ -892,6 +929,7 @@ def propagate(csr: DeviceCSR, X: torch.Tensor, K: int, out=None, use_plan=True, 
     # (csr, plan, launch flags of the group): groups 1.. continue group 0's chains
     parts = [(c, cp, cp.hub_flags() | (SPMM_ACCUMULATE if g else 0))
              for g, (c, cp) in enumerate(parts)]
+    wide = [wide_args(c, cp, 0, n, wide_ts) for c, cp, _ in parts]
     ldw = aligned_ld(F)
     with torch.cuda.device(X.device):
         if native_loop:  # the same loop inside one C ABI call (sgc_propagate_groups_f32)
@@ -906,14 +944,17 @@ def propagate(csr: DeviceCSR, X: torch.Tensor, K: int, out=None, use_plan=True, 
             n_hub = (ctypes.c_int64 * Gn)(*[cp.n_hub for _, cp, _ in parts])
             ths = (ctypes.c_int32 * Gn)(*[cp.threshold for _, cp, _ in parts])
             pflags = (ctypes.c_uint32 * Gn)(*[cp.hub_flags() for _, cp, _ in parts])
+            nonempty = (ctypes.c_int64 * Gn)(*[cp.n_nonempty for _, cp, _ in parts])
+            not_wide = (ctypes.c_int64 * Gn)(*[w[0] for w in wide])
             row_ptrs = parts[0][0].row_ptr  # groups: row 0 of the [G, n+1] row_ptrs tensor
-            _lib.check(lib.sgc_propagate_groups_f32(
+            _lib.check(lib.sgc_propagate_groups_f32_ex3(
                 Gn, _lib.ptr(row_ptrs), _lib.ptr(parts[0][0].col_idx), _lib.ptr(parts[0][0].val), n,
                 _lib.ptr(X), X.stride(0), _lib.ptr(out), out.stride(0), F, int(K),
                 ctypes.cast(plans, ctypes.c_void_p) if planned else None,
                 ctypes.cast(n_heavy, ctypes.c_void_p), ctypes.cast(n_hub, ctypes.c_void_p),
                 ctypes.cast(ths, ctypes.c_void_p), ctypes.cast(pflags, ctypes.c_void_p),
-                _lib.ptr(ws), ws_bytes, stream), "propagate_groups_f32")
+                ctypes.cast(nonempty, ctypes.c_void_p), ctypes.cast(not_wide, ctypes.c_void_p),
+                max(w[1] for w in wide), _lib.ptr(ws), ws_bytes, stream), "propagate_groups_f32")
             return out
         pad = _needs_pad(X) and (pad_pays(csr, F) if PAD_X0 is None else bool(PAD_X0))
         # buffers actually used: the re-laid X_0 (if any) + up to two
@@ -939,13 +980,13 @@ def propagate(csr: DeviceCSR, X: torch.Tensor, K: int, out=None, use_plan=True, 
                      (SPMM_Y_PADDED if dst is not out else 0) | x_flags(src))
             if hop_hook:
                 hop_hook("start", h)
-            for c, cp, gflags in parts:  # column groups: 0 plain, 1.. accumulate
+            for (c, cp, gflags), w in zip(parts, wide):  # column groups: 0 plain, 1.. accumulate
                 args = (_lib.ptr(c.row_ptr), _lib.ptr(c.col_idx), _lib.ptr(c.val), 0, n,
                         _lib.ptr(src), src.stride(0), _lib.ptr(dst), dst.stride(0), F,
                         _lib.ptr(cp.rows), cp.n_heavy, cp.n_hub, cp.threshold, flags | gflags,
-                        cp.n_nonempty)
+                        cp.n_nonempty, *w)
                 ops.append(("spmm", args, slot(src), slot(dst)))
-                _lib.check(lib.sgc_spmm_csr_f32_ex2(*args, stream), "spmm_csr_f32")
+                _lib.check(lib.sgc_spmm_csr_f32_ex3(*args, stream), "spmm_csr_f32")
             if hop_hook:
                 hop_hook("end", h)
             src, nxt = dst, nxt ^ 1
@@ -973,7 +1014,7 @@ class LaunchList:
             if kind == "pad":
                 rc = lib.sgc_launch_list_add_pad_rows(self.handle, *args, s_src, s_dst)
             else:
-                rc = lib.sgc_launch_list_add_spmm_ex2(self.handle, *args, s_src, s_dst)
+                rc = lib.sgc_launch_list_add_spmm_ex3(self.handle, *args, s_src, s_dst)
             _lib.check(rc, "launch_list_add")
 
     def __del__(self):
