@@ -86,7 +86,11 @@ const char *sgc_last_error(void);
  *                   column blocks up to 48 classes, else the fp32 MFMA
  *                   slabs), 1 = fp32 MFMA slabs, 2 = split-bf16 slabs where X
  *                   gives 8-B lanes (K and ldx even), 3 = split-bf16 column
- *                   blocks (up to 48 classes; more: as 0);
+ *                   blocks (up to 48 classes; more: as 0).  The split-bf16
+ *                   kernels need finite X and dY: a non-finite x gives NaN
+ *                   in its column of dW.  torch's non-finite semantics need
+ *                   the fp32 kernels on both sides: "linear_kernel" = 2 AND
+ *                   "backward_kernel" = 1;
  *   "short_wide":   wide items of the multi-row SpMM kernel: a light row of at
  *                   most Ts nonzeros crosses every feature slice in one wave
  *                   instead of one wave per slice (sgc_spmm_csr_f32_ex3).  -1
@@ -563,12 +567,15 @@ int sgc_linear_backward_f32(const float *X, int64_t ldx, const float *dY, int64_
  * gradient.  logits [M, C] (row stride ldl, C <= 64), labels int64 [M]; rows
  * whose label equals ignore_index are left out of the mean (torch's
  * default is -100).  Forward: *loss = mean over the counted rows of
- * lse_m - logits[m, y_m], lse[m] = log sum_c exp(logits[m, c]) (kept for the
- * backward), *inv_count = 1 / (counted rows); NaN loss for a label outside
+ * lse_m - logits[m, y_m], lse[m] = log sum_c exp(logits[m, c]) (an output;
+ * the backward takes the pointer but recomputes the row's max and sum),
+ * *inv_count = 1 / (counted rows); NaN loss for a label outside
  * [0, C).  Backward: dlogits = (softmax - onehot) * (*grad_loss) *
  * (*inv_count) (grad_loss may be NULL: 1), zero rows for ignored labels.
  * Device scalars throughout (no host synchronisation).  Deterministic;
- * tolerance-equal to torch (rtol 1e-5).  workspace:
+ * tolerance-equal to torch (rtol 1e-5) whatever the logits' magnitude: the
+ * loss term is (max - logits[m, y_m]) + log(sum) and the softmax
+ * exp(logits - max) / sum, neither formed from the rounded lse.  workspace:
  * sgc_cross_entropy_workspace(M, C) bytes. */
 int64_t sgc_cross_entropy_workspace(int64_t M, int64_t C);
 int sgc_cross_entropy_f32(const float *logits, int64_t ldl, const int64_t *labels, int64_t M,

@@ -10,12 +10,20 @@
 //   ce_fwd_kernel     16 lanes per row (4 rows per wave, classes l, l+16, l+32,
 //                     l+48 per lane, so C <= 64): row max and sum of exp by
 //                     xor shuffles inside the 16-lane group, lse[row] stored,
-//                     (lse - y[label]) summed in double per workgroup with the
-//                     count of counted rows -> one partial per workgroup;
+//                     (max - y[label]) + log(sum) summed in double per
+//                     workgroup with the count of counted rows -> one partial
+//                     per workgroup;
 //   ce_finish_kernel  the partials in a fixed order (deterministic run to
 //                     run): loss = sum / count and 1 / count;
-//   ce_bwd_kernel     dY = (exp(Y - lse) - onehot(y)) * grad * (1 / count),
-//                     zero rows for ignored labels.
+//   ce_bwd_kernel     dY = (exp(Y - max) / sum - onehot(y)) * grad * (1 / count)
+//                     with the row's max and sum taken again in its 16-lane
+//                     group, zero rows for ignored labels.
+// Softmax does not depend on a common offset of a row's logits, and neither
+// does this arithmetic: lse = max + log(sum) is rounded to ulp(|lse|), so
+// lse - y[label] and exp(Y - lse) carried a relative error of |lse| * 6e-8
+// into the loss and every probability (1e-3 of a gradient at logits near
+// 30,000; tests/test_gpu_classifier_exact.py).  The lse output keeps its
+// meaning; nothing is computed from it.
 // A label outside [0, C) (and not ignore_index) makes the loss NaN (torch
 // stops with a device assert there).
 #include <algorithm>
@@ -71,13 +79,13 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float *__restrict__ Y
         for (int q = 0; q < 4; ++q)
             if (l + 16 * q < C) s += expf(v[q] - m);
         s = group16_sum(s);
-        const float L = m + logf(s);
+        const float ls = logf(s);
         const int64_t y = labels[row];
         if (l == 0) {
-            lse[row] = L;
+            lse[row] = m + ls;
             if (y != ignore_index) {
                 const float yv = (y >= 0 && y < C) ? yr[y] : NAN;
-                acc += (double)(L - yv);
+                acc += (double)((m - yv) + ls);  // m - yv: no rounding of |lse| in it
                 ++cnt;
             }
         }
@@ -130,7 +138,6 @@ __global__ __launch_bounds__(256) void ce_finish_kernel(const double *__restrict
 
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const float *__restrict__ Y, int64_t ldy,
                                                      const int64_t *__restrict__ labels,
-                                                     const float *__restrict__ lse,
                                                      const float *__restrict__ inv_count,
                                                      const float *__restrict__ grad, int M, int C,
                                                      int64_t ignore_index, float *__restrict__ dY,
@@ -144,11 +151,29 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float *__restrict__ Y
         float *dr = dY + row * lddy;
         const int64_t y = labels[row];
         const bool ign = y == ignore_index;
-        const float L = lse[row];
+        // the row's max and sum of exp again (the forward's arithmetic, the
+        // whole 16-lane group in every shuffle): exp(z - max) / sum, never
+        // exp(z - lse) -- see the note at the top
+        float e[4];
+        float m = -INFINITY;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int c = l + 16 * q;
-            if (c < C) dr[c] = ign ? 0.0f : (expf(yr[c] - L) - (c == y ? 1.0f : 0.0f)) * scale;
+            e[q] = c < C ? yr[c] : -INFINITY;
+            m = fmaxf(m, e[q]);
+        }
+        m = group16_max(m);
+        float s = 0.0f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            e[q] = l + 16 * q < C ? expf(e[q] - m) : 0.0f;
+            s += e[q];
+        }
+        s = group16_sum(s);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int c = l + 16 * q;
+            if (c < C) dr[c] = ign ? 0.0f : (e[q] / s - (c == y ? 1.0f : 0.0f)) * scale;
         }
     }
 }
@@ -197,7 +222,9 @@ int cross_entropy_bwd_f32(const float *Y, int64_t ldy, const int64_t *labels, co
     SGC_REQUIRE(M > 0 && M < INT32_MAX && C > 0 && C <= 64 && ldy >= C && lddy >= C, SGC_EINVAL,
                 "cross_entropy_bwd: bad shape M=%lld C=%lld (0 < C <= 64)", (long long)M,
                 (long long)C);
-    hipLaunchKernelGGL(ce_bwd_kernel, dim3(ce_blocks(M)), dim3(256), 0, s, Y, ldy, labels, lse,
+    // (lse: the forward's output, part of the ABI; the kernel takes the row's
+    // max and sum again instead of reading it)
+    hipLaunchKernelGGL(ce_bwd_kernel, dim3(ce_blocks(M)), dim3(256), 0, s, Y, ldy, labels,
                        inv_count, grad, (int)M, (int)C, ignore_index, dY, lddy);
     const hipError_t e = hipGetLastError();
     SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "cross_entropy_bwd launch failed: %s",

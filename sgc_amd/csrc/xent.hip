@@ -80,10 +80,18 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(
                 }
                 mx = group16_max(mx);
                 float se = 0.f;
+                float ez[NT];
 #pragma unroll
-                for (int n = 0; n < NT; ++n) se += valid[n] ? expf(z[n] - mx) : 0.f;
+                for (int n = 0; n < NT; ++n) {
+                    ez[n] = valid[n] ? expf(z[n] - mx) : 0.f;
+                    se += ez[n];
+                }
                 se = group16_sum(se);
-                const float lse = mx + logf(se);
+                // p = exp(z - max) / sum and loss = (max - z_y) + log(sum): as
+                // softmax itself, independent of a common offset of the row
+                // (lse = max + log(sum), rounded to ulp(|lse|), put |lse| * 6e-8
+                // into exp(z - lse) and lse - z_y; loss.hip's note)
+                const float ls = logf(se);
                 const int64_t y = row_ok ? labels[m] : -1;
                 float zy = 0.f;
 #pragma unroll
@@ -91,7 +99,7 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(
                     const int c = n * 16 + i;
                     const bool is_y = (c == y);
                     if (is_y) zy = z[n];
-                    const float p = valid[n] ? expf(z[n] - lse) : 0.f;
+                    const float p = ez[n] / se;
                     const float gv = row_ok ? (p - (is_y ? 1.f : 0.f)) * inv_m : 0.f;
                     if (row_ok) {
                         G[(int64_t)m * ldg + c] = gv;
@@ -100,7 +108,7 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(
                     dbc[n] += gv;
                 }
                 zy = group16_sum(zy);  // exactly one lane of the group holds z_y
-                if (row_ok && i == 0) wave_loss += (double)(lse - zy);
+                if (row_ok && i == 0) wave_loss += (double)((mx - zy) + ls);
             }
     }
     // per-wave partials: loss (lanes i==0 of each group), dG column sums

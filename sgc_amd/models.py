@@ -20,10 +20,16 @@ Non-finite inputs: the GPU forward's split-bf16 kernel (the default for
 M >= 4096 where W fits LDS) needs finite features and weights within bf16's
 range (|x| <= 3.39e38): an infinite (or larger) x or w inside the K range
 gives NaN in its row's logits where torch gives +-inf (tests pin it:
-test_linear_split_nonfinite_inside_k).  SGC's propagated features are finite;
-a caller that needs torch's non-finite semantics selects the fp32 kernel with
-sgc_set_tuning("linear_kernel", 2).
+test_linear_split_nonfinite_inside_k).  The weight backward is split-bf16 by
+default as well (the column-block kernel, up to 48 classes, at any M): a
+non-finite x gives NaN in its column of dW for every class, where torch gives
++-inf or NaN by the signs (test_backward_nonfinite_features).  SGC's
+propagated features are finite; a caller that needs torch's non-finite
+semantics selects the fp32 kernels on both sides, with
+sgc_set_tuning("linear_kernel", 2) AND sgc_set_tuning("backward_kernel", 1).
 """
+import weakref
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -120,7 +126,13 @@ class _LogitsCrossEntropy(torch.autograd.Function):
         return dY, None, None
 
 
-_checked_labels = {}
+_checked_labels = {}  # id(labels) -> (weak reference, (version, C, ignore_index))
+
+
+def _forget_labels(ref, key):
+    hit = _checked_labels.get(key)
+    if hit is not None and hit[0] is ref:
+        del _checked_labels[key]
 
 
 def _check_labels(labels, C, ignore_index):
@@ -129,9 +141,14 @@ def _check_labels(labels, C, ignore_index):
     return NaN and poison the optimiser's weights.  One check (and one host
     synchronisation) per labels tensor and version: the reference closures
     pass the same labels tensor on every call (citation.py:46-49,
-    reddit.py:55-58), so LBFGS's 20-odd closures per step pay it once."""
-    key = (labels.data_ptr(), labels._version, labels.shape[0], int(C), int(ignore_index))
-    if key in _checked_labels:
+    reddit.py:55-58), so LBFGS's 20-odd closures per step pay it once.  The
+    pass belongs to the tensor object (a weak reference, dropped when the
+    tensor dies), never to its address: a new labels tensor that the allocator
+    places in a freed one's block is checked like any other."""
+    key = id(labels)
+    state = (labels._version, int(C), int(ignore_index))
+    hit = _checked_labels.get(key)
+    if hit is not None and hit[0]() is labels and hit[1] == state:
         return
     bad = ((labels < 0) | (labels >= C)) & (labels != ignore_index)
     if bool(bad.any()):
@@ -140,7 +157,7 @@ def _check_labels(labels, C, ignore_index):
                          f"{ignore_index})")
     if len(_checked_labels) > 64:
         _checked_labels.clear()
-    _checked_labels[key] = True
+    _checked_labels[key] = (weakref.ref(labels, lambda r, key=key: _forget_labels(r, key)), state)
 
 
 def _cross_entropy_args(args, kwargs):

@@ -806,8 +806,11 @@ def test_logits_cross_entropy_rejects_out_of_range_labels():
         with pytest.raises(IndexError, match="out of bounds"):
             torch.nn.functional.cross_entropy(model(x), y_bad)
     n = len(models._checked_labels)
+    entry = models._checked_labels[id(y)]  # the pass belongs to the tensor object
+    assert entry[0]() is y and entry[1] == (y._version, 5, -100)
     torch.nn.functional.cross_entropy(model(x), y)
     assert len(models._checked_labels) == n  # cached: no second check
+    assert models._checked_labels[id(y)] is entry
 
 
 def test_linear_split_precision_vs_fp32_mfma():
