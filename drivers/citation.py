@@ -3,14 +3,18 @@ reference's citation.py (same flags via get_citation_args, same output
 lines), reading Planetoid files from ./data like the reference.
 
     python drivers/citation.py --dataset cora [--tuned] [--degree 2] [--epochs 100]
+                               [--feature-dtype {float32,bfloat16,float16}]
 
 Flow (reference citation.py:14-70): seed -> load_citation -> SGC model
 (created before the precompute, so the RNG draws for W match) ->
 sgc_precompute on the GPU -> Adam over the training rows -> accuracy.
 --tuned uses the tuned weight decays of the reference's SGC-tuning/ results
 (values recorded in SURVEY.md section 2, row 11; the pickled files are not
-read).
+read).  --feature-dtype (this driver's own flag, default float32) casts the
+loaded features once: the propagated features, the training rows and the
+evaluation rows stay in that type, the weights and logits in float32.
 """
+import argparse
 import os
 import sys
 from time import perf_counter
@@ -26,6 +30,7 @@ from sgc_amd.metrics import accuracy  # noqa: E402
 from sgc_amd.models import get_model  # noqa: E402
 from sgc_amd.utils import load_citation, set_seed, sgc_precompute  # noqa: E402
 
+FEATURE_DTYPES = {"float32": torch.float32, "bfloat16": torch.bfloat16, "float16": torch.float16}
 TUNED_WEIGHT_DECAY = {"cora": 1.3027e-05, "citeseer": 2.3546e-05, "pubmed": 7.4039e-05}
 
 
@@ -53,6 +58,9 @@ def test_regression(model, test_features, test_labels):
 
 def main(argv=None):
     args = get_citation_args(argv)
+    own = argparse.ArgumentParser(add_help=False)
+    own.add_argument("--feature-dtype", choices=sorted(FEATURE_DTYPES), default="float32")
+    feature_dtype = FEATURE_DTYPES[own.parse_known_args(argv)[0].feature_dtype]
     if args.tuned:
         if args.model != "SGC":
             raise NotImplementedError("tuned hyper-parameters exist for SGC only")
@@ -63,6 +71,8 @@ def main(argv=None):
         args.dataset, args.normalization, args.cuda)
     model = get_model(args.model, features.size(1), labels.max().item() + 1, args.hidden,
                       args.dropout, args.cuda)
+    if feature_dtype != torch.float32:
+        features = features.to(feature_dtype)
     features, precompute_time = sgc_precompute(features, adj, args.degree)
     print("{:.4f}s".format(precompute_time))
     model, acc_val, train_time = train_regression(

@@ -31,6 +31,9 @@ NORMALIZATIONS = ["NormLap", "Lap", "RWalkLap", "FirstOrderGCN", "AugNormAdj", "
                   "AugRWalk", "NoNorm"]
 
 
+FEATURE_DTYPES = {"float32": torch.float32, "bfloat16": torch.bfloat16, "float16": torch.float16}
+
+
 def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--no-cuda", action="store_true", default=False, help="Disables CUDA training.")
@@ -47,6 +50,9 @@ def parse(argv=None):
                    help="use a seeded Reddit-shape synthetic graph with this many nodes (0: read data/)")
     p.add_argument("--device-lbfgs", action="store_true", default=False,
                    help="train with sgc_amd.optim.LBFGS (no host synchronisation per iteration)")
+    p.add_argument("--feature-dtype", choices=sorted(FEATURE_DTYPES), default="float32",
+                   help="storage type of the features: cast once after loading; the propagated "
+                        "features, the training and the evaluation rows stay in it")
     args = p.parse_args(argv)
     args.cuda = not args.no_cuda and torch.cuda.is_available()
     return args
@@ -114,6 +120,8 @@ def main(argv=None):
         adj, train_adj, features, labels, idx_train, idx_val, idx_test = \
             load_reddit_data(args.normalization)
     print("Finished data loading.")
+    if args.feature_dtype != "float32":
+        features = features.to(FEATURE_DTYPES[args.feature_dtype])
     model = SGC(features.size(1), labels.max().item() + 1)
     if args.cuda:
         model.cuda()

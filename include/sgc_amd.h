@@ -561,6 +561,34 @@ int sgc_linear_backward_f32(const float *X, int64_t ldx, const float *dY, int64_
                             int64_t M, int64_t K, int64_t C, float *dW, float *db,
                             void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The classifier on 16-bit features: X is torch.bfloat16 / torch.float16
+ * memory (x_dtype = SGC_DTYPE_BF16 / SGC_DTYPE_F16; anything else returns
+ * SGC_EINVAL with an sgc_last_error text before any pointer is touched); W, b,
+ * dY, Y, dW and db stay fp32.  Results are defined on the exactly widened
+ * elements -- Y = float(X) W^T + b, dW = dY^T float(X), db = sum dY -- and
+ * nothing is rounded to 16 bits: a bf16 x is one bf16 piece (3 MFMAs per class
+ * tile, nothing dropped), an fp16 x exactly two (5 MFMAs), W and dY three as
+ * in the fp32 kernels.  A non-finite x inside the K range gives non-finite
+ * results in its row of Y / its column of dW, not necessarily torch's +-inf;
+ * padding past K may hold anything.
+ * Covered: even element pitch ldx, X 4-B aligned, M * ldx * 2 < 2^31, and for
+ * the forward every class block (64 classes at a time) with its W image
+ * within LDS (K = 602: C <= 42), at any M >= 1; for the backward C <= 48.
+ * Anything else returns SGC_EINVAL and the name functions return "none":
+ * there is no fp32 kernel behind these entry points.  workspace:
+ * sgc_linear_backward_x16_workspace(M, K, C) bytes.  The unit is not part of
+ * sgc_warmup. */
+int sgc_linear_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *W, const float *b,
+                   float *Y, int64_t ldy, int64_t M, int64_t K, int64_t C, void *stream);
+const char *sgc_linear_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,
+                                       const void *X, int32_t x_dtype);
+int64_t sgc_linear_backward_x16_workspace(int64_t M, int64_t K, int64_t C);
+int sgc_linear_backward_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *dY, int64_t ldd,
+                            int64_t M, int64_t K, int64_t C, float *dW, float *db,
+                            void *ws, int64_t ws_bytes, void *stream);
+const char *sgc_linear_backward_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,
+                                                const void *X, int32_t x_dtype);
+
 /* Softmax cross-entropy over a logits matrix: the loss the reference's
  * closures take of the classifier's output, F.cross_entropy(model(x), y)
  * with mean reduction (citation.py:46-49, reddit.py:55-58), and its

@@ -124,6 +124,12 @@ SIGNATURES = {
     "sgc_linear_backward_workspace": (_i64, [_i64, _i64, _i64]),
     "sgc_linear_backward_f32": (ctypes.c_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p,
                                                _i64, _p]),
+    "sgc_linear_x16": (ctypes.c_int, [_p, _i32, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _p]),
+    "sgc_linear_x16_kernel_name": (ctypes.c_char_p, [_i64, _i64, _i64, _i64, _p, _i32]),
+    "sgc_linear_backward_x16_workspace": (_i64, [_i64, _i64, _i64]),
+    "sgc_linear_backward_x16": (ctypes.c_int, [_p, _i32, _i64, _p, _i64, _i64, _i64, _i64, _p, _p,
+                                               _p, _i64, _p]),
+    "sgc_linear_backward_x16_kernel_name": (ctypes.c_char_p, [_i64, _i64, _i64, _i64, _p, _i32]),
     "sgc_lbfgs_workspace": (_i64, [_i64, _i32]),
     "sgc_lbfgs_init": (ctypes.c_int, [_p, _i64, _i64, _i32, _p]),
     "sgc_lbfgs_begin_step": (ctypes.c_int, [_p, _p]),

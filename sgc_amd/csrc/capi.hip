@@ -106,6 +106,16 @@ const char *linear_backward_kernel_name(int64_t M, int64_t K, int64_t ldx, int64
                                         const float *X);
 int launch_linear_f32(const float *X, int64_t ldx, const float *W, const float *b, float *Y,
                       int64_t ldy, int64_t M, int64_t K, int64_t C, hipStream_t stream);
+const char *linear_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C, const void *X,
+                                   int32_t x_dtype);
+int launch_linear_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *W, const float *b,
+                      float *Y, int64_t ldy, int64_t M, int64_t K, int64_t C, hipStream_t stream);
+const char *linear_backward_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,
+                                            const void *X, int32_t x_dtype);
+int64_t linear_backward_x16_workspace_bytes(int64_t M, int64_t K, int64_t C);
+int linear_backward_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *dY, int64_t ldd,
+                        int64_t M, int64_t K, int64_t C, float *dW, float *db, void *ws,
+                        int64_t ws_bytes, hipStream_t s);
 int64_t plan_sorted_workspace(int64_t n_rows);
 int plan_sorted(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
                 int32_t hub_threshold, int32_t *plan, void *workspace, int64_t workspace_bytes,
@@ -652,6 +662,32 @@ int sgc_linear_backward_f32(const float *X, int64_t ldx, const float *dY, int64_
                             int64_t workspace_bytes, void *stream) {
     return linear_backward_f32(X, ldx, dY, ldd, M, K, C, dW, db, workspace, workspace_bytes,
                                as_stream(stream));
+}
+
+int sgc_linear_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *W, const float *b,
+                   float *Y, int64_t ldy, int64_t M, int64_t K, int64_t C, void *stream) {
+    return launch_linear_x16(X, x_dtype, ldx, W, b, Y, ldy, M, K, C, as_stream(stream));
+}
+
+const char *sgc_linear_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C, const void *X,
+                                       int32_t x_dtype) {
+    return linear_x16_kernel_name(M, K, ldx, C, X, x_dtype);
+}
+
+int64_t sgc_linear_backward_x16_workspace(int64_t M, int64_t K, int64_t C) {
+    return linear_backward_x16_workspace_bytes(M, K, C);
+}
+
+int sgc_linear_backward_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *dY,
+                            int64_t ldd, int64_t M, int64_t K, int64_t C, float *dW, float *db,
+                            void *ws, int64_t ws_bytes, void *stream) {
+    return linear_backward_x16(X, x_dtype, ldx, dY, ldd, M, K, C, dW, db, ws, ws_bytes,
+                               as_stream(stream));
+}
+
+const char *sgc_linear_backward_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,
+                                                const void *X, int32_t x_dtype) {
+    return linear_backward_x16_kernel_name(M, K, ldx, C, X, x_dtype);
 }
 
 int64_t sgc_cross_entropy_workspace(int64_t M, int64_t C) { return cross_entropy_workspace(M, C); }

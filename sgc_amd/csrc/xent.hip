@@ -870,6 +870,18 @@ hipError_t launch_dw_cols(const float *X, int64_t ldx, const float *G, int ldg, 
 
 }  // namespace
 
+// xent_reduce_dw_db_kernel over n_parts partials of the column-block layout
+// (db skipped when null) for the 16-bit-feature backward of linear16.hip,
+// whose kernel writes the same partials.
+hipError_t launch_reduce_dw_db(const float *slab, int n_parts, int C, int K, int C16, float *dW,
+                               const float *db_slab, float *db, hipStream_t s) {
+    const int dw_blocks = (int)(((int64_t)C * K + 63) / 64);
+    const int db_blocks = db ? (C + 3) / 4 : 0;  // a wave per class
+    hipLaunchKernelGGL(xent_reduce_dw_db_kernel, dim3((unsigned)(dw_blocks + db_blocks)),
+                       dim3(256), 0, s, slab, n_parts, C, K, C16, dW, db_slab, db, dw_blocks);
+    return hipGetLastError();
+}
+
 // Backward kernel choice (sgc_set_tuning("backward_kernel")): 0 auto (the
 // split-bf16 column blocks up to 48 classes, the fp32 MFMA slabs above), 1 the
 // fp32 MFMA slabs, 2 the split-bf16 slabs where X gives 8-B lanes, 3 the

@@ -27,6 +27,22 @@ non-finite x gives NaN in its column of dW for every class, where torch gives
 propagated features are finite; a caller that needs torch's non-finite
 semantics selects the fp32 kernels on both sides, with
 sgc_set_tuning("linear_kernel", 2) AND sgc_set_tuning("backward_kernel", 1).
+
+16-bit features: x may be torch.bfloat16 or torch.float16 (what
+sgc_precompute(X.bfloat16(), adj, K) stores); the weights, the bias, the
+logits and the weight gradients stay float32.  The model computes
+float(x) W^T + b on the exactly widened elements -- nothing is rounded to 16
+bits -- on the x16 kernels (sgc_linear_x16, sgc_linear_backward_x16; see
+propagate.linear / linear_backward for the copy and upcast paths of layouts
+and shapes they do not cover), on CPU tensors as F.linear(x.float(), W, b).
+A gradient with respect to the features, if asked for, has x's dtype on both
+devices.  The x16 kernels share the split kernels' non-finite deviation at
+every M: a non-finite x inside the K range gives non-finite logits in its
+row and a non-finite column of dW, not necessarily torch's +-inf (an infinite
+fp16 x splits into inf and inf - inf; an infinite x times a zero piece of w
+is NaN); no tuning selects torch's semantics for 16-bit x short of x.float().
+The fused sgc_linear_xent_f32 step stays float32-only: sgc_cross_entropy on
+16-bit features takes the unfused expression.
 """
 import weakref
 
@@ -49,14 +65,15 @@ class _LinearMFMA(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         x, weight = ctx.saved_tensors
-        gx = grad_out @ weight if ctx.needs_input_grad[0] else None
+        # (the features' gradient in their own dtype: float32, or x's 16 bits)
+        gx = (grad_out @ weight).to(x.dtype) if ctx.needs_input_grad[0] else None
         gw = gb = None
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1] or want_b:
             if weight.shape[0] <= 64:
                 gw, gb = _mfma_linear_backward(x, grad_out, want_bias=want_b)
             else:  # wider than the fused kernel's 64 classes
-                gw = grad_out.t() @ x
+                gw = grad_out.t() @ x.to(grad_out.dtype)
                 gb = grad_out.sum(0) if want_b else None
             if not ctx.needs_input_grad[1]:
                 gw = None
@@ -219,8 +236,9 @@ def sgc_cross_entropy(model, features, labels):
     GPU: one launch chain computes the loss and the W/b gradients (the
     reference closure, citation.py:47-49 / reddit.py:55-58).  Works with Adam
     and LBFGS exactly like the unfused expression.  CPU tensors take the
-    unfused expression itself."""
-    if features.device.type == "cpu":
+    unfused expression itself, and so do 16-bit features on either device (the
+    fused step is float32-only)."""
+    if features.device.type == "cpu" or features.dtype in (torch.bfloat16, torch.float16):
         return F.cross_entropy(model(features), labels)
     return _LinearCrossEntropy.apply(features, model.W.weight, model.W.bias, labels)
 
@@ -234,6 +252,8 @@ class SGC(nn.Module):
 
     def forward(self, x):
         if x.device.type == "cpu":  # reference arithmetic (models.py:18)
+            if x.dtype in (torch.bfloat16, torch.float16):  # on the widened elements
+                return F.linear(x.float(), self.W.weight, self.W.bias)
             return self.W(x)
         # (a logits tensor whose F.cross_entropy runs on the HIP kernels)
         return _LinearMFMA.apply(x, self.W.weight, self.W.bias).as_subclass(SGCLogits)

@@ -1179,23 +1179,85 @@ def collect_launch_timing(capacity=1 << 16):
             [names.get(int(kind[i])) for i in range(k)])
 
 
+def _even_pitch_x16(X):
+    """A 16-bit X in a layout the x16 classifier kernels take: unit column
+    stride, even element pitch, 4-B aligned base -- X itself when it already
+    is, else one copy into an even-pitch buffer (an odd K such as Cora's 1433
+    or Citeseer's 3703 in a contiguous tensor, or a view that starts on an odd
+    element)."""
+    M, K = X.shape
+    if X.stride(1) == 1 and X.stride(0) >= K and X.stride(0) % 2 == 0 and X.data_ptr() % 4 == 0:
+        return X
+    buf = torch.empty((M, K + (K & 1)), dtype=X.dtype, device=X.device)
+    buf[:, :K].copy_(X)
+    return buf[:, :K]
+
+
+def _linear_x16(X, W, b, out):
+    """The 16-bit-feature forward, or None where sgc_linear_x16 does not cover
+    the shape (the caller upcasts)."""
+    lib = _lib.load()
+    M, K = X.shape
+    C = W.shape[0]
+    dt = X16_DTYPES[X.dtype]
+
+    def named(t):
+        return lib.sgc_linear_x16_kernel_name(M, K, t.stride(0), C, _lib.ptr(t), dt) != b"none"
+
+    if M == 0:
+        return out
+    if not (X.stride(1) == 1 and X.stride(0) >= K and named(X)):
+        X = _even_pitch_x16(X)  # a layout problem alone: one copy
+        if not named(X):
+            return None
+    if M * out.stride(0) * 4 >= 2 ** 31:
+        return None
+    with torch.cuda.device(X.device):
+        _lib.check(lib.sgc_linear_x16(_lib.ptr(X), dt, X.stride(0), _lib.ptr(W), _lib.ptr(b),
+                                      _lib.ptr(out), out.stride(0), M, K, C,
+                                      _lib.stream_handle(X.device)), "linear_x16")
+    return out
+
+
 def linear(X: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, out=None):
-    """Y = X . W^T + b on fp32 MFMA (reference models.py:17-18, nn.Linear)."""
+    """Y = X . W^T + b on MFMA (reference models.py:17-18, nn.Linear); W, b and
+    Y (``out``) are float32.
+
+    float32 X runs sgc_linear_f32.  torch.bfloat16 / torch.float16 X gives
+    Y = float(X) . W^T + b on the exactly widened elements (nothing is rounded
+    to 16 bits):
+    * where sgc_linear_x16_kernel_name names a kernel for X as it lies in
+      memory, sgc_linear_x16 reads the 16-bit rows directly;
+    * a layout problem alone -- an odd element pitch or a 2-B-aligned base,
+      e.g. a contiguous [N, 1433] or [N, 3703] tensor -- is fixed by one copy
+      into an even-pitch 16-bit buffer, then the same kernel;
+    * a shape the kernel does not cover (a class block whose W image exceeds
+      LDS, e.g. K = 602 with 49 classes; offsets past 31 bits) takes
+      X.float() and the float32 path.
+    A non-finite x inside the K range gives non-finite logits in its row, not
+    necessarily torch's +-inf."""
     _require_device(X, "input")
-    if X.dtype != torch.float32 or weight.dtype != torch.float32:
-        raise TypeError("sgc_amd.linear: float32 only")
+    if weight.dtype != torch.float32 or not (X.dtype == torch.float32 or is_x16(X)):
+        raise TypeError("sgc_amd.linear: float32, bfloat16 or float16 features and float32 "
+                        "weights only")
     if X.dim() != 2:
         raise ValueError("sgc_amd.linear: 2-D input expected")
     M, K = X.shape
     C = weight.shape[0]
     if weight.shape[1] != K:
         raise RuntimeError(f"sgc_amd.linear: shape mismatch {tuple(X.shape)} x {tuple(weight.shape)}^T")
-    if X.stride(1) != 1 or X.stride(0) < K:
-        X = X.contiguous()
     W = weight.contiguous()
     b = bias.contiguous() if bias is not None else None
     if out is None:
         out = torch.empty((M, C), dtype=torch.float32, device=X.device)
+    if is_x16(X):
+        if out.dtype != torch.float32:
+            raise TypeError("sgc_amd.linear: out must be float32")
+        if _linear_x16(X, W, b, out) is not None:
+            return out
+        X = X.float()  # not covered: the float32 kernels on the widened copy
+    if X.stride(1) != 1 or X.stride(0) < K:
+        X = X.contiguous()
     lib = _lib.load()
     with torch.cuda.device(X.device):
         _lib.check(lib.sgc_linear_f32(_lib.ptr(X), X.stride(0), _lib.ptr(W), _lib.ptr(b),
@@ -1206,17 +1268,27 @@ def linear(X: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
 
 def linear_backward(X: torch.Tensor, grad_out: torch.Tensor, want_bias=True):
     """(dW, db) of Y = X W^T + b for dY = grad_out: dW = dY^T X, db = sum_m dY
-    (None unless want_bias), one read of X on fp32 MFMA
-    (sgc_linear_backward_f32).  At most 64 classes."""
+    (None unless want_bias), one read of X on MFMA.  At most 64 classes; dY, dW
+    and db are float32.
+
+    float32 X runs sgc_linear_backward_f32.  torch.bfloat16 / torch.float16 X
+    gives dW = dY^T . float(X) on the exactly widened elements:
+    * up to 48 classes sgc_linear_backward_x16 reads the 16-bit rows directly
+      where sgc_linear_backward_x16_kernel_name names a kernel;
+    * a layout problem alone (odd element pitch, 2-B-aligned base) is fixed by
+      one copy into an even-pitch 16-bit buffer, then the same kernel;
+    * above 48 classes, or past 31-bit offsets, it takes X.float() and the
+      float32 path.
+    A non-finite x gives a non-finite column of dW, not necessarily torch's
+    +-inf."""
     _require_device(X, "input")
     M, K = X.shape
     C = grad_out.shape[1]
-    if grad_out.shape[0] != M or X.dtype != torch.float32 or grad_out.dtype != torch.float32:
+    if (grad_out.shape[0] != M or not (X.dtype == torch.float32 or is_x16(X)) or
+            grad_out.dtype != torch.float32):
         raise RuntimeError("sgc_amd.linear_backward: shape/dtype mismatch")
     if C > 64:
         raise ValueError("sgc_amd.linear_backward: at most 64 classes")
-    if X.stride(1) != 1 or X.stride(0) < K:
-        X = X.contiguous()
     if grad_out.stride(1) != 1 or grad_out.stride(0) < C:
         grad_out = grad_out.contiguous()
     dW = torch.empty((C, K), dtype=torch.float32, device=X.device)
@@ -1227,6 +1299,28 @@ def linear_backward(X: torch.Tensor, grad_out: torch.Tensor, want_bias=True):
             db.zero_()
         return dW, db
     lib = _lib.load()
+    if is_x16(X):
+        dt = X16_DTYPES[X.dtype]
+
+        def named(t):
+            return lib.sgc_linear_backward_x16_kernel_name(M, K, t.stride(0), C, _lib.ptr(t),
+                                                           dt) != b"none"
+
+        X16 = X
+        if not (X16.stride(1) == 1 and X16.stride(0) >= K and named(X16)):
+            X16 = _even_pitch_x16(X16) if C <= 48 else None
+        if X16 is not None and named(X16) and 32 * grad_out.stride(0) * 4 < 2 ** 31:
+            ws_bytes = lib.sgc_linear_backward_x16_workspace(M, K, C)
+            ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=X.device)
+            with torch.cuda.device(X.device):
+                _lib.check(lib.sgc_linear_backward_x16(
+                    _lib.ptr(X16), dt, X16.stride(0), _lib.ptr(grad_out), grad_out.stride(0), M, K,
+                    C, _lib.ptr(dW), _lib.ptr(db), _lib.ptr(ws), ws_bytes,
+                    _lib.stream_handle(X.device)), "linear_backward_x16")
+            return dW, db
+        X = X.float()  # not covered: the float32 kernels on the widened copy
+    if X.stride(1) != 1 or X.stride(0) < K:
+        X = X.contiguous()
     ws_bytes = lib.sgc_linear_backward_workspace(M, K, C)
     ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=X.device)
     with torch.cuda.device(X.device):
