@@ -227,6 +227,13 @@ int sgc_plan_light_order(const int32_t *row_ptr, int64_t row_begin, int64_t row_
  *     acc = +0.0f; for k in row i (CSR order): acc = fmaf(val[k], X[col[k], f], acc)
  * -- bit-identical to the reference CPU kernel.  X rows have stride ldx
  * floats, Y rows ldy floats; X must not alias Y.
+ * Special values (IEEE 754 binary32, no flush to zero, on every schedule):
+ * Y[i,f] is NaN exactly where the reference's result is NaN; the payload and
+ * the sign of a NaN are unspecified.  Every other element is bit-equal,
+ * signed zeros (a chain whose products all underflow to -0 ends in -0.0; an
+ * empty row gives +0.0), subnormal operands and results, and overflow to
+ * +-inf included.  No FMA is issued beyond the row's stored entries: a pad
+ * lane or a re-read last nonzero never reaches a chain.
  * plan/n_heavy/n_hub/heavy_threshold from sgc_plan_build over the same row
  * range, or plan = NULL (one work item per row, natural order).
  * ------------------------------------------------------------------------- */
@@ -503,6 +510,10 @@ int64_t sgc_aligned_ld(int64_t F);
  *     sgc_spmm_csr_f32(S, (float)X) converted to T,
  * and a K-hop loop through 16-bit buffers to K such hops; the plan (plan,
  * n_heavy, n_hub, heavy_threshold, as sgc_spmm_csr_f32) is a schedule only.
+ * Special values, as for sgc_spmm_csr_f32: NaN exactly where that definition
+ * gives NaN (payload and sign unspecified), every other 16-bit pattern equal
+ * -- signed zeros and the 16-bit format's subnormals included -- on every
+ * schedule.
  * flags: the bits of sgc_spmm_csr_f32_ex.  For a 16-bit operand the padded
  * flags mean columns [F, round8(F)) (readable in X / writable in Y);
  * the 4 GiB flag means n_cols * ldx * 2 < 2^32; the accumulate flag
