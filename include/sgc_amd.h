@@ -137,17 +137,24 @@ int sgc_csr64_to_csr(const int64_t *crow, const int64_t *col, const float *vals,
 
 /* ---------------------------------------------------------------------------
  * On-device augmented normalisation S = D^-1/2 (A+I) D^-1/2 (reference
- * normalization.py:5-12 + the fp32 rounding of utils.py:25), bit-exact with
- * scipy's result.  A: canonical CSR (ascending unique columns per row), fp64
- * values.  Two passes around one host step, exactly as the reference splits
- * its arithmetic:
- *   1. sgc_augnorm_count: per-row entry count of A+I -> out_row_ptr (scan) and
- *      rowsum (fp64, sequential in column order); *out_nnz_host = nnz(S).
+ * normalization.py:5-12 + the fp32 rounding of utils.py:25): scipy's entries
+ * and, where its value is not NaN, its fp32 bits (NaN where it is NaN; payload
+ * and sign unspecified).  A: canonical CSR (ascending unique columns per row),
+ * fp64 values.  Two passes around one host step, exactly as the reference
+ * splits its arithmetic:
+ *   1. sgc_augnorm_count: per-row entry count of A+I (exact zeros pruned: a
+ *      stored +-0.0 of A, a_ii + 1 == 0) -> out_row_ptr (scan) and rowsum
+ *      (fp64, sequential in column order); *out_nnz_host = nnz(A+I).
  *      Synchronous.  Returns SGC_EINVAL if A is not canonical.
  *   2. host: d = rowsum ** -0.5, inf -> 0 (numpy, as normalization.py:8-10);
+ *      d is 0 for a sum of 0 or +-inf, NaN for a negative or NaN sum;
  *   3. sgc_augnorm_fill: S entries (d_i * a_ij) * d_j in fp64 -> fp32, in
- *      ascending column order, dropping exact zeros like scipy's csr_matmat
- *      (out_row_ptr may shrink then; *out_nnz_host = final nnz).  Synchronous.
+ *      ascending column order.  An entry is dropped, as scipy's
+ *      diags(d) . (A+I) . diags(d) drops it, when d_i == 0, d_j == 0,
+ *      d_i * a_ij == 0 or the product == 0 -- decided in fp64, so 0 * inf and
+ *      0 * NaN leave no entry while a product that only rounds to 0.0f stays
+ *      one (out_row_ptr may shrink then; *out_nnz_host = final nnz).
+ *      Synchronous.
  * workspace: sgc_augnorm_workspace(n) bytes of device scratch.
  * ------------------------------------------------------------------------- */
 int64_t sgc_augnorm_workspace(int64_t n_rows);
@@ -166,7 +173,7 @@ int sgc_augnorm_fill(const int32_t *row_ptr, const int32_t *col_idx, const doubl
  * A: CSR (int32), fp64 values; idx: int64 [m], distinct ids in [0, n_rows).
  * B: canonical CSR (new row i = old row idx[i], new column = position in
  * idx, ascending), fp64 values -- the input sgc_augnorm_count/fill take, so
- * the S_train built from B is the reference's bit for bit.  Two synchronous
+ * the S_train built from B is the reference's (as above).  Two synchronous
  * calls around the host allocation of B, sharing one workspace:
  *   sgc_subgraph_count: out_row_ptr [m+1], *out_nnz_host = nnz(B);
  *     status_host bits: 1 = repeated ids (SGC_EINVAL), 2 = idx ascending,

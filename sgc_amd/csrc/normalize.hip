@@ -3,20 +3,32 @@
 // SURVEY.md 8(f) row 1 "next" item: at Reddit shape the reference's host
 // scipy pass costs ~7 s, against a ~13 ms propagation.
 //
-// Bit-exact contract with the reference (scipy 1.15 semantics, restated):
+// Contract with the reference (scipy 1.15 semantics, restated).  S has the
+// reference's entries and, where the reference's value is not NaN, its fp32
+// bits; where it is NaN ours is NaN (payload and sign unspecified, as for the
+// SpMM):
 //   * A is canonical CSR (ascending unique columns per row), fp64 values;
 //   * A+I: the diagonal entry becomes a_ii + 1.0 (inserted as 1.0 at its
-//     sorted position when absent); a result of exactly 0.0 is dropped, as
-//     scipy's csr binop prunes zeros;
+//     sorted position when absent); every entry of A takes part in the add, so
+//     a result of exactly 0.0 -- a stored +-0.0 too -- is dropped, as scipy's
+//     csr binop prunes zeros;
 //   * rowsum_i = sequential fp64 sum of row i of A+I in column order (scipy's
 //     coo matvec in storage order);
 //   * d = rowsum ** -0.5 with inf -> 0 is computed on the HOST with numpy, as
-//     the reference does (sgc_amd/normalization.py drives these kernels);
-//   * s_ij = (d_i * a_ij) * d_j in fp64 (two csr_matmat passes), entries equal
-//     to 0.0 dropped (csr_matmat prunes zeros), then rounded once to fp32.
-// Pass 1 counts each row's A+I entries and sums it; pass 2 writes S.  A row
-// whose S entries include zeros (only when some d is 0) is rare; pass 2
-// reports them and a compaction pass (pass 3) removes them, keeping order.
+//     the reference does (sgc_amd/normalization.py drives these kernels); d is
+//     0 for a row summing to 0 or +-inf and NaN for a negative or NaN sum;
+//   * s_ij = (d_i * a_ij) * d_j in fp64, from diags(d) . (A+I) . diags(d): the
+//     dia -> csr conversion stores no d == 0, and each of the two csr_matmat
+//     passes prunes exact zeros.  An entry is therefore dropped when
+//         d_i == 0  or  d_j == 0  or  d_i * a_ij == 0  or  (d_i * a_ij) * d_j == 0
+//     (so 0 * inf and 0 * NaN are dropped, not kept as NaN), decided in fp64;
+//   * the kept products are rounded once to fp32: one that rounds to 0.0f, a
+//     subnormal or +-inf stays an entry.
+// Pass 1 counts each row's A+I entries and sums it; pass 2 writes S and marks
+// each dropped entry with a negative column (-1 - j); rows with such entries
+// are rare (some d is 0, or a product underflows fp64), pass 2 reports them
+// and a compaction pass (pass 3) removes exactly the marked entries, keeping
+// order.
 #include "common.h"
 
 #include <hipcub/hipcub.hpp>
@@ -87,11 +99,15 @@ __global__ void augnorm_fill_kernel(const int32_t *__restrict__ row_ptr,
         const int32_t k0 = row_ptr[i], k1 = row_ptr[i + 1];
         const double di = d[i];
         int32_t o = out_ptr[i];
-        bool diag_done = false, any_zero = false;
+        bool diag_done = false, any_drop = false;
         auto emit = [&](int32_t j, double a) {
-            const double s = (di * a) * d[j];
-            any_zero |= (s == 0.0);
-            out_col[o] = j;
+            const double dj = d[j];
+            const double t = di * a;
+            const double s = t * dj;
+            // the reference's rule, in fp64 (NaN compares unequal to 0: kept)
+            const bool drop = di == 0.0 || dj == 0.0 || t == 0.0 || s == 0.0;
+            any_drop |= drop;
+            out_col[o] = drop ? -1 - j : j;
             out_val[o] = (float)s;
             ++o;
         };
@@ -109,34 +125,32 @@ __global__ void augnorm_fill_kernel(const int32_t *__restrict__ row_ptr,
             if (a != 0.0) emit(j, a);
         }
         if (!diag_done) emit((int32_t)i, 1.0);
-        zero_rows[i] = any_zero ? 1 : 0;
+        zero_rows[i] = any_drop ? 1 : 0;
     }
 }
 
-// Drop the entries of S that are exactly 0 (fp64 product), keeping order.
+// Drop the entries the fill pass marked (negative column), keeping order.
 __global__ void augnorm_zero_count_kernel(const int32_t *__restrict__ ptr,
-                                          const float *__restrict__ v64_sign_source,
-                                          const int32_t *__restrict__ zero_rows, int64_t n,
+                                          const int32_t *__restrict__ col, int64_t n,
                                           int32_t *__restrict__ counts) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
         int32_t c = 0;
-        for (int32_t k = ptr[i]; k < ptr[i + 1]; ++k) c += v64_sign_source[k] != 0.0f || !zero_rows[i];
+        for (int32_t k = ptr[i]; k < ptr[i + 1]; ++k) c += col[k] >= 0;
         counts[i] = c;
     }
 }
 
 __global__ void augnorm_compact_kernel(const int32_t *__restrict__ ptr,
                                        const int32_t *__restrict__ col,
-                                       const float *__restrict__ val,
-                                       const int32_t *__restrict__ zero_rows, int64_t n,
+                                       const float *__restrict__ val, int64_t n,
                                        const int32_t *__restrict__ new_ptr,
                                        int32_t *__restrict__ out_col, float *__restrict__ out_val) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
         int32_t o = new_ptr[i];
         for (int32_t k = ptr[i]; k < ptr[i + 1]; ++k)
-            if (val[k] != 0.0f || !zero_rows[i]) {
+            if (col[k] >= 0) {
                 out_col[o] = col[k];
                 out_val[o] = val[k];
                 ++o;
@@ -224,7 +238,7 @@ int augnorm_fill(const int32_t *row_ptr, const int32_t *col, const double *val, 
     hipLaunchKernelGGL(augnorm_fill_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, s, row_ptr, col,
                        val, n, d, out_row_ptr, out_col, out_val, zero_rows);
     SGC_HIP_CHECK(hipGetLastError());
-    // any row with a zero product?  (only when some d is 0: rows summing to 0)
+    // any row with a dropped entry?
     int32_t nz_total = 0;
     {
         size_t tb = tmp_bytes;
@@ -251,13 +265,13 @@ int augnorm_fill(const int32_t *row_ptr, const int32_t *col, const double *val, 
         SGC_HIP_CHECK(hipMemcpyAsync(ptr_tmp, out_row_ptr, sizeof(int32_t) * (n + 1),
                                      hipMemcpyDeviceToDevice, s));
         hipLaunchKernelGGL(augnorm_zero_count_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, s,
-                           ptr_tmp, val_tmp, zero_rows, n, counts);
+                           ptr_tmp, col_tmp, n, counts);
         SGC_HIP_CHECK(hipGetLastError());
         int64_t t64 = 0;
         int rc = scan_counts(counts, n, out_row_ptr, tmp, tmp_bytes, s, &t64);
         if (rc) return rc;
         hipLaunchKernelGGL(augnorm_compact_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, s,
-                           ptr_tmp, col_tmp, val_tmp, zero_rows, n, out_row_ptr, out_col, out_val);
+                           ptr_tmp, col_tmp, val_tmp, n, out_row_ptr, out_col, out_val);
         SGC_HIP_CHECK(hipGetLastError());
         SGC_HIP_CHECK(hipFreeAsync(col_tmp, s));
         SGC_HIP_CHECK(hipFreeAsync(val_tmp, s));

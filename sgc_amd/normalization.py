@@ -2,14 +2,20 @@
 reference's normalization.py.
 
 The values of S decide the arithmetic of the whole hot path, so this module
-reproduces the reference's numbers bit for bit (pinned by
-tests/test_dropin.py::test_aug_normalized_adjacency_matches_reference against
-the reference module itself, and on the device by tests/test_gpu_normalize.py
-against the reference's S hashes):
+reproduces the reference's S: the same entries, and after the fp32 cast the
+same bits wherever the reference's value is not NaN (NaN where it is NaN;
+payload and sign unspecified).  Pinned by tests/test_dropin.py and
+tests/test_graph_edges_cpu.py against what the reference module itself
+returned, and on the device by tests/test_gpu_normalize.py (the reference's S
+hashes) and tests/test_gpu_graph_edges.py:
 
 * aug_normalized_adjacency (reference normalization.py:5-12):
   S = D^-1/2 (A + I) D^-1/2 with D = rowsum(A + I), all in fp64;
-  d = rowsum ** -0.5 via np.power, inf -> 0; entry = (d_i * a_ij) * d_j;
+  A + I prunes exact zeros (stored zeros of A, a_ii + 1 == 0);
+  d = rowsum ** -0.5 via np.power, inf -> 0 (NaN for a negative sum);
+  entry = (d_i * a_ij) * d_j, dropped -- as the reference's
+  diags(d) . (A + I) . diags(d) drops it -- when d_i == 0, d_j == 0,
+  d_i * a_ij == 0 or the product == 0, so 0 * inf and 0 * NaN leave no NaN;
   entries in canonical CSR order (row-major, ascending column).
 * row_normalize (reference normalization.py:21-28): X <- diag(1/rowsum) X,
   inf -> 0.
@@ -22,7 +28,7 @@ import scipy.sparse as sp
 
 
 def _inv_power(v, p):
-    with np.errstate(divide="ignore"):
+    with np.errstate(divide="ignore", invalid="ignore"):  # 0 -> inf, negative -> NaN
         out = np.power(v, p)
     out[np.isinf(out)] = 0.0
     return out
@@ -32,11 +38,19 @@ def aug_normalized_adjacency(adj):
     a = sp.csr_matrix(adj + sp.eye(adj.shape[0]))
     a.sum_duplicates()
     a.sort_indices()
-    rowsum = np.asarray(a.sum(axis=1), dtype=np.float64).ravel()
+    # the reference sums the COO form: a sequential fp64 sum in column order
+    # (csr's own sum(axis=1) is numpy's pairwise reduceat, another rounding)
+    with np.errstate(invalid="ignore", over="ignore"):
+        rowsum = np.asarray(a.tocoo().sum(axis=1), dtype=np.float64).ravel()
     d = _inv_power(rowsum, -0.5)
     rows = np.repeat(np.arange(a.shape[0]), np.diff(a.indptr))
-    data = (d[rows] * a.data.astype(np.float64)) * d[a.indices]
-    return sp.coo_matrix((data, (rows, a.indices.copy())), shape=a.shape)
+    di, dj = d[rows], d[a.indices]
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        t = di * a.data.astype(np.float64)
+        data = t * dj
+    # dia -> csr stores no d == 0; each csr_matmat pass prunes exact zeros
+    keep = (di != 0.0) & (dj != 0.0) & (t != 0.0) & (data != 0.0)
+    return sp.coo_matrix((data[keep], (rows[keep], a.indices[keep])), shape=a.shape)
 
 
 _NORMALIZERS = {"AugNormAdj": aug_normalized_adjacency}
@@ -55,8 +69,9 @@ def row_normalize(mx):
 
 
 def aug_normalize_on_device(adj, device="cuda"):
-    """S = AugNorm(A) computed on the GPU (libsgc_amd: sgc_augnorm_count/fill),
-    bit-identical to aug_normalized_adjacency(A) -> fp32.  Returns a
+    """S = AugNorm(A) computed on the GPU (libsgc_amd: sgc_augnorm_count/fill):
+    the entries of aug_normalized_adjacency(A) and the bits of its fp32 cast
+    (NaN where that is NaN), the same drop rule included.  Returns a
     sgc_amd.propagate.DeviceCSR ready for propagation.
 
     A must be canonical CSR (scipy's has_canonical_format: sorted, unique
@@ -91,7 +106,8 @@ def subgraph_on_device(rp, ci, va, n, idx):
     train sub-graph), from device_csr64 arrays: canonical CSR with fp64 values
     (new row i = old row idx[i], new column = position in idx), ready for
     aug_normalize_device_arrays -- whose S is then the reference's
-    fetch_normalization('AugNormAdj')(adj[idx, :][:, idx]) bit for bit.
+    fetch_normalization('AugNormAdj')(adj[idx, :][:, idx]) (same entries, same
+    fp32 bits where not NaN).
     Repeated ids raise ValueError (the host slice handles them)."""
     import torch
 

@@ -530,10 +530,11 @@ def to_torch_coo(csr: DeviceCSR):
     lib = _lib.load()
     nnz = csr.nnz
     idx = torch.empty((2, nnz), dtype=torch.int64, device=csr.device)
-    with torch.cuda.device(csr.device):
-        _lib.check(lib.sgc_csr_to_coo64(_lib.ptr(csr.row_ptr), _lib.ptr(csr.col_idx), csr.n_rows,
-                                        _lib.ptr(idx[0]), _lib.ptr(idx[1]),
-                                        _lib.stream_handle(csr.device)), "csr_to_coo64")
+    if nnz > 0:  # an empty S (every row summing to 0) has no index storage to fill
+        with torch.cuda.device(csr.device):
+            _lib.check(lib.sgc_csr_to_coo64(_lib.ptr(csr.row_ptr), _lib.ptr(csr.col_idx),
+                                            csr.n_rows, _lib.ptr(idx[0]), _lib.ptr(idx[1]),
+                                            _lib.stream_handle(csr.device)), "csr_to_coo64")
     adj = torch.sparse_coo_tensor(idx, csr.val, (csr.n_rows, csr.n_cols))
     try:
         adj._sgc_amd_csr = (adj._version, csr)

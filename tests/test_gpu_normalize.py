@@ -1,4 +1,6 @@
-"""On-device AugNorm vs the reference's S, bit for bit.
+"""On-device AugNorm vs the reference's S, bit for bit
+(graphs with positive row sums; signed and special weights, where entries are
+dropped and NaN appears, are in tests/test_gpu_graph_edges.py).
 
 The golden shape hashes (tests/golden/shapes.json) are of S exactly as the
 reference builds it (normalization.py:5-12 + utils.py:23-30); the host
@@ -60,7 +62,9 @@ def _cases():
     D = sp.csr_matrix((n, n))
     out["empty"] = D
     E = sp.lil_matrix((6, 6))
-    E[0, 0] = -1.0  # a_00 + 1 == 0 -> pruned; row 0 sums to 0 -> d_0 = 0
+    # a_00 + 1 == 0 is pruned by A + I; a_03 = 1 stays, so row 0 sums to 1 and no d is 0
+    # (zero-sum rows: tests/graph_edge_cases.py)
+    E[0, 0] = -1.0
     E[0, 3] = 1.0
     E[1, 2] = 2.0
     E[2, 1] = 2.0
