@@ -3,7 +3,7 @@ reference's citation.py (same flags via get_citation_args, same output
 lines), reading Planetoid files from ./data like the reference.
 
     python drivers/citation.py --dataset cora [--tuned] [--degree 2] [--epochs 100]
-                               [--feature-dtype {float32,bfloat16,float16}]
+                               [--feature-dtype {float32,bfloat16,float16}] [--device-adam]
 
 Flow (reference citation.py:14-70): seed -> load_citation -> SGC model
 (created before the precompute, so the RNG draws for W match) ->
@@ -13,6 +13,9 @@ sgc_precompute on the GPU -> Adam over the training rows -> accuracy.
 read).  --feature-dtype (this driver's own flag, default float32) casts the
 loaded features once: the propagated features, the training rows and the
 evaluation rows stay in that type, the weights and logits in float32.
+--device-adam (also this driver's own) trains with sgc_amd.optim.Adam's
+run_epochs: the same loop, enqueued on the GPU by one host call; without it
+the loop below runs through torch.optim.Adam as before.
 """
 import argparse
 import os
@@ -35,15 +38,23 @@ TUNED_WEIGHT_DECAY = {"cora": 1.3027e-05, "citeseer": 2.3546e-05, "pubmed": 7.40
 
 
 def train_regression(model, train_features, train_labels, val_features, val_labels,
-                     epochs, weight_decay, lr, dropout):
-    optimizer = optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
-    t = perf_counter()
-    for _ in range(epochs):
-        model.train()
-        optimizer.zero_grad()
-        loss = F.cross_entropy(model(train_features), train_labels)
-        loss.backward()
-        optimizer.step()
+                     epochs, weight_decay, lr, dropout, device_adam=False):
+    if device_adam:  # the whole loop below in one host call (sgc_amd/optim.py)
+        from sgc_amd.optim import Adam
+        optimizer = Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
+        t = perf_counter()
+        optimizer.run_epochs(model, train_features, train_labels, epochs)
+        if train_features.device.type == "cuda":
+            torch.cuda.synchronize(train_features.device)  # the epochs are only enqueued
+    else:
+        optimizer = optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
+        t = perf_counter()
+        for _ in range(epochs):
+            model.train()
+            optimizer.zero_grad()
+            loss = F.cross_entropy(model(train_features), train_labels)
+            loss.backward()
+            optimizer.step()
     train_time = perf_counter() - t
     with torch.no_grad():
         model.eval()
@@ -60,7 +71,10 @@ def main(argv=None):
     args = get_citation_args(argv)
     own = argparse.ArgumentParser(add_help=False)
     own.add_argument("--feature-dtype", choices=sorted(FEATURE_DTYPES), default="float32")
-    feature_dtype = FEATURE_DTYPES[own.parse_known_args(argv)[0].feature_dtype]
+    own.add_argument("--device-adam", action="store_true", default=False,
+                     help="train with sgc_amd.optim.Adam.run_epochs (the epochs in one host call)")
+    own_args = own.parse_known_args(argv)[0]
+    feature_dtype = FEATURE_DTYPES[own_args.feature_dtype]
     if args.tuned:
         if args.model != "SGC":
             raise NotImplementedError("tuned hyper-parameters exist for SGC only")
@@ -77,7 +91,8 @@ def main(argv=None):
     print("{:.4f}s".format(precompute_time))
     model, acc_val, train_time = train_regression(
         model, features[idx_train], labels[idx_train], features[idx_val], labels[idx_val],
-        args.epochs, args.weight_decay, args.lr, args.dropout)
+        args.epochs, args.weight_decay, args.lr, args.dropout,
+        **({"device_adam": True} if own_args.device_adam else {}))  # (absent: the call as before)
     acc_test = test_regression(model, features[idx_test], labels[idx_test])
     print("Validation Accuracy: {:.4f} Test Accuracy: {:.4f}".format(acc_val, acc_test))
     print("Pre-compute time: {:.4f}s, train time: {:.4f}s, total: {:.4f}s".format(

@@ -2,7 +2,9 @@
 
 Put dropin/ first on sys.path (or PYTHONPATH) and `from optim import LBFGS`
 gives the device-resident L-BFGS with torch.optim.LBFGS's constructor, for the
-reference's reddit.py:52 (`optim.LBFGS(model.parameters(), lr=1)`).  See
+reference's reddit.py:52 (`optim.LBFGS(model.parameters(), lr=1)`), and
+`from optim import Adam` the device-resident Adam with torch.optim.Adam's
+constructor and a run_epochs() for the loop of citation.py:41-50.  See
 INTEGRATION.md.
 """
 import os as _os

@@ -103,7 +103,14 @@ const char *sgc_last_error(void);
  *                   "short_wide_launches" = launches that took wide items,
  *                   "short_wide_state" = (knob + 1) * 64 + Ts in one read;
  *   "short_wide_first": 1 = the wide waves' workgroups come first in the
- *                   grid, 0 (default) = last.
+ *                   grid, 0 (default) = last;
+ *   "adam_kernel":  schedule of sgc_train_adam_f32, 0 = auto (the small
+ *                   schedule where it measured faster: M <= 313 and
+ *                   16 M < K + 832), 1 = general, 2 = small (a
+ *                   shape it cannot take runs the general one).  Read-only
+ *                   beside it: "adam_kernel_last" = the schedule the last
+ *                   call ran (1 / 2; 0 before the first) and
+ *                   "adam_small_max_rows" = the small schedule's row limit.
  * sgc_get_tuning returns -1 for an unknown key. */
 int sgc_set_tuning(const char *key, int64_t value);
 int64_t sgc_get_tuning(const char *key);
@@ -714,6 +721,67 @@ int sgc_lbfgs_iterate_f32(void *state, int32_t n_tensors, float *const *param_pt
 int sgc_lbfgs_read_status(const void *state, int64_t *out_host, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Device-resident Adam: optim.Adam of citation.py:41-50 (torch's default
+ * single-tensor math: amsgrad=False, maximize=False, coupled L2 weight decay).
+ *
+ * Per element, in fp32 with one rounding per operation, in this order:
+ *     g' = g + wd * p                       (skipped when wd == 0)
+ *     m  = m + (g' - m) * (1 - b1)
+ *     v  = b2 * v + ((1 - b2) * g') * g'
+ *     denom = sqrt(v) / sqrt(1 - b2^step) + eps
+ *     p  = p - (lr / (1 - b1^step)) * (m / denom)
+ * wd, 1 - b1, b2, 1 - b2, eps, sqrt(1 - b2^step) and lr / (1 - b1^step) are
+ * computed on the host in double and rounded to fp32 once; sqrt and the
+ * divisions are correctly rounded, no product is contracted into a sum.
+ * Bitwise reproducible run to run; tolerance-equal to torch, not bit-equal.
+ *
+ *   sgc_adam_step_f32: one launch updates n_tensors (1..16) contiguous fp32
+ *     tensors of numels_host[i] elements, p, exp_avg and exp_avg_sq in place;
+ *     the host tables travel as kernel arguments.  A NULL gradient entry
+ *     skips that tensor entirely (torch skips a parameter whose .grad is
+ *     None; its state does not move).  step: the count after this update
+ *     (>= 1).  Asynchronous, never synchronises.
+ *
+ *   sgc_train_adam_f32: the loop of citation.py:44-50 -- zero_grad, model(x),
+ *     F.cross_entropy, backward, Adam.step -- for the SGC classifier
+ *     z = X W^T + b, `epochs` times, enqueued on `stream` by one host call: no
+ *     host synchronisation, no allocation, no atomics, every sum in a fixed
+ *     order.  Epoch e uses Adam step step0 + e + 1 (step0 >= 0).  W [C, K],
+ *     b [C] and their moments are updated in place; b and its two moments
+ *     may be NULL together.  loss_trace: `epochs` device floats or NULL;
+ *     loss_trace[e] is the mean cross-entropy at the weights before epoch e's
+ *     update.  C <= 64; labels must lie in [0, C) (not checked on the device;
+ *     the Python layer checks them).  X needs a 4-B aligned base and
+ *     ldx >= K only.  workspace: sgc_train_adam_workspace(M, K, C) bytes (0
+ *     for an empty shape or C > 64).
+ *     Two schedules (sgc_set_tuning "adam_kernel"): the general one, any M,
+ *     is launches A and B of sgc_linear_xent_f32 and one launch that reduces
+ *     the dW, db and loss partials in sgc_linear_xent_f32's orders and applies
+ *     the update in the threads holding the finished gradient elements (three
+ *     launches per epoch); the small one, M <= 313, runs two launches per
+ *     epoch over 64-column blocks of K with plain fp32 fmaf sums (partial
+ *     logits per block, then softmax, dW of the block over all rows and the
+ *     update).  313 rows is what one workgroup's 160 KB of LDS hold of
+ *     G = softmax - onehot ([M][65] floats at 64 classes) next to its X tile
+ *     ([M][64]) and 2 KB of scratch: (163,840 - 2,048) / 516.  The two
+ *     schedules sum in different orders: tolerance-equal, not bit-equal.
+ * Argument errors return SGC_EINVAL / SGC_ERANGE / SGC_ENOMEM (workspace)
+ * with an sgc_last_error text before any device call.
+ * ------------------------------------------------------------------------- */
+int sgc_adam_step_f32(int32_t n_tensors, float *const *param_ptrs_host,
+                      const float *const *grad_ptrs_host, float *const *exp_avg_ptrs_host,
+                      float *const *exp_avg_sq_ptrs_host, const int64_t *numels_host,
+                      int64_t step, double lr, double beta1, double beta2, double eps,
+                      double weight_decay, void *stream);
+int64_t sgc_train_adam_workspace(int64_t M, int64_t K, int64_t C);
+int sgc_train_adam_f32(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels,
+                       int64_t M, int64_t K, int64_t C,
+                       float *exp_avg_W, float *exp_avg_sq_W, float *exp_avg_b, float *exp_avg_sq_b,
+                       int64_t step0, int32_t epochs, double lr, double beta1, double beta2,
+                       double eps, double weight_decay, float *loss_trace,
+                       void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Host (CPU) twins, for CPU tensors: the reference runs utils.py:92-97 on the
  * CPU whenever CUDA is off (args.py:39 --no-cuda; load_citation(cuda=False)).
  * Every pointer here is a HOST pointer; the calls are synchronous and
@@ -850,7 +918,7 @@ int sgc_mgpu_finalize(void);
  * `stream` (the current device) and waits for them, so those loads happen
  * here rather than inside the first sgc_precompute the caller times
  * (reddit.py:43,72-74).  Units: SGC_WARM_PROPAGATE = SpMM, ingest, plan,
- * sort, column groups, the exchanges' block copy; SGC_WARM_CLASSIFIER = linear, fused loss, cross-entropy, L-BFGS;
+ * sort, column groups, the exchanges' block copy; SGC_WARM_CLASSIFIER = linear, fused loss, cross-entropy, L-BFGS, Adam;
  * SGC_WARM_LOADERS = normalisation, sub-graph.  Synchronous. */
 enum { SGC_WARM_PROPAGATE = 1, SGC_WARM_CLASSIFIER = 2, SGC_WARM_LOADERS = 4 };
 int sgc_warmup(uint32_t units, void *stream);

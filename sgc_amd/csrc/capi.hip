@@ -4,6 +4,7 @@
 #include <mutex>
 #include <vector>
 #include <cstdio>
+#include <cstring>
 
 #include "common.h"
 
@@ -149,6 +150,19 @@ int lbfgs_iterate(void *state, int32_t n_tensors, float *const *params, const fl
                   const int64_t *numels, const float *loss, double lr, int32_t max_iter,
                   int32_t max_eval, double tol_grad, double tol_change, hipStream_t s);
 int lbfgs_read_status(const void *state, int64_t *out_host, hipStream_t s);
+extern int g_adam_kernel, g_adam_kernel_last;
+int adam_set_tuning(int64_t value);
+int64_t adam_small_max_rows();
+int adam_step(int32_t n_tensors, float *const *params, const float *const *grads,
+              float *const *exp_avgs, float *const *exp_avg_sqs, const int64_t *numels,
+              int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
+              hipStream_t s);
+int64_t train_adam_workspace(int64_t M, int64_t K, int64_t C);
+int train_adam(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels, int64_t M,
+               int64_t K, int64_t C, float *mW, float *vW, float *mb, float *vb, int64_t step0,
+               int32_t epochs, double lr, double beta1, double beta2, double eps,
+               double weight_decay, float *loss_trace, void *ws, int64_t ws_bytes, hipStream_t s);
+hipError_t warm_adam(hipStream_t);
 
 }  // namespace sgc
 
@@ -160,9 +174,18 @@ int sgc_abi_version(void) { return SGC_ABI_VERSION; }
 
 const char *sgc_last_error(void) { return g_err; }
 
-int sgc_set_tuning(const char *key, int64_t value) { return set_tuning(key, value); }
+// ("adam_kernel" / "adam_kernel_last" belong to adam.hip; every other key to spmm.hip's table)
+int sgc_set_tuning(const char *key, int64_t value) {
+    if (key && std::strcmp(key, "adam_kernel") == 0) return adam_set_tuning(value);
+    return set_tuning(key, value);
+}
 
-int64_t sgc_get_tuning(const char *key) { return get_tuning(key); }
+int64_t sgc_get_tuning(const char *key) {
+    if (key && std::strcmp(key, "adam_kernel") == 0) return g_adam_kernel;
+    if (key && std::strcmp(key, "adam_kernel_last") == 0) return g_adam_kernel_last;
+    if (key && std::strcmp(key, "adam_small_max_rows") == 0) return adam_small_max_rows();
+    return get_tuning(key);
+}
 
 int sgc_coo_to_csr_workspace(int64_t n_rows, int64_t nnz, size_t *bytes_host) {
     return coo_to_csr_workspace(n_rows, nnz, bytes_host);
@@ -744,6 +767,30 @@ int sgc_lbfgs_read_status(const void *state, int64_t *out_host, void *stream) {
     return lbfgs_read_status(state, out_host, as_stream(stream));
 }
 
+int sgc_adam_step_f32(int32_t n_tensors, float *const *param_ptrs_host,
+                      const float *const *grad_ptrs_host, float *const *exp_avg_ptrs_host,
+                      float *const *exp_avg_sq_ptrs_host, const int64_t *numels_host, int64_t step,
+                      double lr, double beta1, double beta2, double eps, double weight_decay,
+                      void *stream) {
+    return adam_step(n_tensors, param_ptrs_host, grad_ptrs_host, exp_avg_ptrs_host,
+                     exp_avg_sq_ptrs_host, numels_host, step, lr, beta1, beta2, eps, weight_decay,
+                     as_stream(stream));
+}
+
+int64_t sgc_train_adam_workspace(int64_t M, int64_t K, int64_t C) {
+    return train_adam_workspace(M, K, C);
+}
+
+int sgc_train_adam_f32(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels,
+                       int64_t M, int64_t K, int64_t C, float *exp_avg_W, float *exp_avg_sq_W,
+                       float *exp_avg_b, float *exp_avg_sq_b, int64_t step0, int32_t epochs,
+                       double lr, double beta1, double beta2, double eps, double weight_decay,
+                       float *loss_trace, void *workspace, int64_t workspace_bytes, void *stream) {
+    return train_adam(X, ldx, W, b, labels, M, K, C, exp_avg_W, exp_avg_sq_W, exp_avg_b,
+                      exp_avg_sq_b, step0, epochs, lr, beta1, beta2, eps, weight_decay, loss_trace,
+                      workspace, workspace_bytes, as_stream(stream));
+}
+
 int sgc_warmup(uint32_t units, void *stream) {
     SGC_REQUIRE((units & ~7u) == 0, SGC_EINVAL, "warmup: unknown unit bits 0x%x", units);
     hipStream_t s = as_stream(stream);
@@ -761,6 +808,7 @@ int sgc_warmup(uint32_t units, void *stream) {
         SGC_HIP_CHECK(warm_xent(s));
         SGC_HIP_CHECK(warm_loss(s));
         SGC_HIP_CHECK(warm_lbfgs(s));
+        SGC_HIP_CHECK(warm_adam(s));
     }
     if (units & SGC_WARM_LOADERS) {
         SGC_HIP_CHECK(warm_normalize(s));

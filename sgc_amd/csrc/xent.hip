@@ -17,7 +17,11 @@
 //                         (A = G^T straight from G's row-major layout,
 //                         B = X rows, V-vector loads split over V MFMAs);
 //   C  xent_reduce_kernel slabs -> dW, per-wave partials -> db and loss, in a
-//                         fixed order (bitwise reproducible run to run).
+//                         fixed order (bitwise reproducible run to run);
+//   C' xent_reduce_adam_kernel (sgc_train_adam_f32's general schedule, adam.hip)
+//                         both reductions of C in one launch, each finished
+//                         gradient element applied to W / b by Adam in place.
+#include "adam_update.h"
 #include "gemm_tile.h"
 #include "split_bf16.h"
 
@@ -816,6 +820,83 @@ __global__ __launch_bounds__(256) void xent_reduce_small_kernel(
     }
 }
 
+// The two reductions above in one launch, with the Adam update
+// (adam_update.h) applied by the thread that holds the finished gradient
+// element -- the last launch of an epoch of sgc_train_adam_f32's general
+// schedule.  Blocks [0, dw_blocks): dW elements in xent_reduce_dw_kernel's
+// order, then W / exp_avg / exp_avg_sq in place; blocks dw_blocks + c (c < C):
+// db[c] in xent_reduce_small_kernel's order, then b[c] (skipped when b is
+// null); block dw_blocks + C: the loss, to *loss_out when non-null.
+__global__ __launch_bounds__(256) void xent_reduce_adam_kernel(
+    const float *__restrict__ slab, int n_slabs, int C, int K, int C16, int dw_blocks,
+    const double *__restrict__ loss_part, const float *__restrict__ db_part, int n_waves,
+    double inv_m, float *__restrict__ W, float *__restrict__ mW, float *__restrict__ vW,
+    float *__restrict__ b, float *__restrict__ mb, float *__restrict__ vb, AdamCoef coef,
+    float *__restrict__ loss_out) {
+    __shared__ float part[4][64];
+    __shared__ double red[256];
+    if ((int)blockIdx.x < dw_blocks) {
+        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+        const int64_t e = blockIdx.x * 64LL + lane;
+        const int64_t total = (int64_t)C * K;
+        const int j0 = (int)((int64_t)n_slabs * w / 4), j1 = (int)((int64_t)n_slabs * (w + 1) / 4);
+        float s = 0.f;
+        if (e < total) {
+            const int64_t cls = e / K, k = e - cls * K;
+            const float *p = slab + cls * K + k;
+            const int64_t stride = (int64_t)C16 * K;
+            int j = j0;
+            for (; j + 8 <= j1; j += 8) {
+                float v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)(j + u) * stride];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) s += v[u];
+            }
+            for (; j < j1; ++j) s += p[(int64_t)j * stride];
+        }
+        part[w][lane] = s;
+        __syncthreads();
+        if (w == 0 && e < total) {
+            const float g = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+            float pw = W[e], m = mW[e], v = vW[e];
+            adam_update(pw, m, v, g, coef);
+            W[e] = pw;
+            mW[e] = m;
+            vW[e] = v;
+        }
+        return;  // (uniform per block)
+    }
+    const int t = threadIdx.x, c = (int)blockIdx.x - dw_blocks;
+    if (c < C && !b) return;
+    if (c == C && !loss_out) return;
+    double s = 0.0;
+    if (c == C) {
+        for (int j = t; j < n_waves; j += 256) s += loss_part[j];
+    } else {
+        float f = 0.f;
+        for (int j = t; j < n_waves; j += 256) f += db_part[(int64_t)j * C16 + c];
+        s = f;
+    }
+    red[t] = s;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h) red[t] += red[t + h];
+        __syncthreads();
+    }
+    if (t == 0) {
+        if (c == C) {
+            *loss_out = (float)(red[0] * inv_m);
+        } else {
+            float pb = b[c], m = mb[c], v = vb[c];
+            adam_update(pb, m, v, (float)red[0], coef);
+            b[c] = pb;
+            mb[c] = m;
+            vb[c] = v;
+        }
+    }
+}
+
 template <int V, int NT>
 hipError_t launch_fwd(const float *X, int64_t ldx, const float *W, const float *b,
                       const int64_t *labels, int M, int K, int C, float *G, int ldg,
@@ -907,6 +988,18 @@ int64_t xent_workspace_bytes(int64_t M, int64_t K, int64_t C) {
     return al(M * C16 * 4) + al(waves * 8) + al(waves * C16 * 4) + al(n_slabs * C16 * K * 4) + 512;
 }
 
+// Where launches A and B leave G and their partials in the workspace.
+struct XentPartials {
+    float *G;
+    double *loss_part;
+    float *db_part;
+    float *slab;
+    int C16, waves, n_parts;
+};
+static int xent_launch_ab(const float *X, int64_t ldx, const float *W, const float *b,
+                          const int64_t *labels, int64_t M, int64_t K, int64_t C, float *logits,
+                          int64_t ldl, void *ws, hipStream_t s, XentPartials &out);
+
 int linear_xent_f32(const float *X, int64_t ldx, const float *W, const float *b,
                     const int64_t *labels, int64_t M, int64_t K, int64_t C, float *loss,
                     float *dW, float *db, float *logits, int64_t ldl, void *ws, int64_t ws_bytes,
@@ -923,6 +1016,25 @@ int linear_xent_f32(const float *X, int64_t ldx, const float *W, const float *b,
     const int64_t need = xent_workspace_bytes(M, K, C);
     SGC_REQUIRE(ws_bytes >= need, SGC_ENOMEM, "linear_xent: workspace %lld < %lld",
                 (long long)ws_bytes, (long long)need);
+    XentPartials part;
+    if (const int rc = xent_launch_ab(X, ldx, W, b, labels, M, K, C, logits, ldl, ws, s, part))
+        return rc;
+    const int64_t ck = C * K;
+    hipLaunchKernelGGL(xent_reduce_dw_kernel, dim3((unsigned)((ck + 63) / 64)), dim3(256), 0, s,
+                       part.slab, part.n_parts, (int)C, (int)K, part.C16, dW);
+    SGC_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(xent_reduce_small_kernel, dim3((unsigned)C + 1), dim3(256), 0, s,
+                       part.loss_part, part.db_part, part.waves, (int)C, part.C16, 1.0 / (double)M,
+                       loss, db);
+    SGC_HIP_CHECK(hipGetLastError());
+    return SGC_OK;
+}
+
+// Launches A and B of the fused step (the caller has checked the shape and the
+// workspace size); `out` says where they left G and the partials.
+static int xent_launch_ab(const float *X, int64_t ldx, const float *W, const float *b,
+                          const int64_t *labels, int64_t M, int64_t K, int64_t C, float *logits,
+                          int64_t ldl, void *ws, hipStream_t s, XentPartials &out) {
     const int NT = (int)((C + 15) / 16);
     const int C16 = NT * 16;
     const int waves = (int)((M + kLdsBM - 1) / kLdsBM * 4);
@@ -989,12 +1101,37 @@ int linear_xent_f32(const float *X, int64_t ldx, const float *W, const float *b,
     }
 #undef SGC_XENT_DISPATCH
     SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "linear_xent launch failed: %s", hipGetErrorString(e));
-    const int64_t ck = C * K;
-    hipLaunchKernelGGL(xent_reduce_dw_kernel, dim3((unsigned)((ck + 63) / 64)), dim3(256), 0, s,
-                       slab, n_parts, (int)C, (int)K, C16, dW);
-    SGC_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(xent_reduce_small_kernel, dim3((unsigned)C + 1), dim3(256), 0, s, loss_part, db_part,
-                       waves, (int)C, C16, 1.0 / (double)M, loss, db);
+    out = XentPartials{G, loss_part, db_part, slab, C16, waves, n_parts};
+    return SGC_OK;
+}
+
+// ---- general schedule of sgc_train_adam_f32 ---------------------------------
+// One epoch: launches A and B as above, then xent_reduce_adam_kernel in place
+// of the two reduce launches.  W (and b) are updated in place; the next
+// epoch's launch A is stream-ordered behind the update.
+int xent_adam_check(int64_t M, int64_t K, int64_t C, int64_t ldx) {
+    SGC_REQUIRE(M < INT32_MAX && K < INT32_MAX, SGC_ERANGE, "train_adam: too large");
+    SGC_REQUIRE(block_tile_fits(ldx, K, C), SGC_ERANGE,
+                "train_adam: ldx=%lld / K=%lld past the tile's 31-bit offsets", (long long)ldx,
+                (long long)K);
+    return SGC_OK;
+}
+
+int xent_adam_epoch(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels,
+                    int64_t M, int64_t K, int64_t C, float *mW, float *vW, float *mb, float *vb,
+                    const AdamCoef &coef, float *loss_out, void *ws, int64_t ws_bytes,
+                    hipStream_t s) {
+    const int64_t need = xent_workspace_bytes(M, K, C);
+    SGC_REQUIRE(ws_bytes >= need, SGC_ENOMEM, "train_adam: workspace %lld < %lld",
+                (long long)ws_bytes, (long long)need);
+    XentPartials part;
+    if (const int rc = xent_launch_ab(X, ldx, W, b, labels, M, K, C, nullptr, 0, ws, s, part))
+        return rc;
+    const int dw_blocks = (int)((C * K + 63) / 64);
+    hipLaunchKernelGGL(xent_reduce_adam_kernel, dim3((unsigned)(dw_blocks + C + 1)), dim3(256), 0,
+                       s, part.slab, part.n_parts, (int)C, (int)K, part.C16, dw_blocks,
+                       part.loss_part, part.db_part, part.waves, 1.0 / (double)M, W, mW, vW, b, mb,
+                       vb, coef, loss_out);
     SGC_HIP_CHECK(hipGetLastError());
     return SGC_OK;
 }

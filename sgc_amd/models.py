@@ -8,7 +8,9 @@ On ROCm tensors the forward GEMM runs on the fp32 MFMA kernel
 one read of X: sgc_linear_backward_f32) on the same MFMA tile -- what the
 reference closures' .backward() needs (citation.py:47-49, reddit.py:55-58);
 dX = dY W (only if the features require a gradient) is a torch op.  Adam
-(citation.py:41) and LBFGS (reddit.py:52) work unchanged.  The ROCm output is
+(citation.py:41) and LBFGS (reddit.py:52) work unchanged; sgc_amd.optim has
+device-resident forms of both (Adam.run_epochs runs the whole citation loop
+on this model in one host call).  The ROCm output is
 an SGCLogits tensor: the closures' unchanged F.cross_entropy(output, labels)
 runs on the HIP cross-entropy kernels (sgc_cross_entropy_f32, one pass for
 the loss, one for the gradient) rather than torch's nll reduction.  On CPU

@@ -22,10 +22,19 @@ models -- is torch.optim.LBFGS.step itself, bit for bit.
 Results of the device path are tolerance-equal to torch's (fp64-accumulated
 dot products in a fixed order; torch sums in fp32) and bitwise reproducible
 run to run.  state_dict() does not carry the device state.
+
+`Adam` is torch.optim.Adam (the citation loop's optimiser, citation.py:41-50)
+with torch's constructor and torch's state layout -- state[p] = {"step",
+"exp_avg", "exp_avg_sq"}, so state_dict() / load_state_dict() round-trip and
+the device path and torch's own step() can alternate on one optimiser.
+step() is one sgc_adam_step_f32 launch per param group; run_epochs() is the
+whole training loop in one host call (sgc_train_adam_f32).  See the class.
 """
 import ctypes
+import weakref
 
 import torch
+import torch.nn.functional as F
 
 from . import _lib
 
@@ -155,3 +164,263 @@ class LBFGS(torch.optim.LBFGS):
         if g.dtype != torch.float32 or g.device != p.device:
             g = g.to(device=p.device, dtype=torch.float32)
         return g.contiguous()
+
+
+_label_checks = {}  # id(labels) -> (weak reference, (version, C), has ignored rows)
+
+
+def _forget_label_check(ref, key):
+    hit = _label_checks.get(key)
+    if hit is not None and hit[0] is ref:
+        del _label_checks[key]
+
+
+def _labels_have_ignored(labels, C):
+    """Range check of run_epochs' labels, once (one host synchronisation) per
+    labels tensor object and version, as models._check_labels keeps its
+    passes: a label outside [0, C) other than -100 raises IndexError as torch
+    does; -> whether any row carries ignore_index (-100), which the fused
+    loop does not compute."""
+    key = id(labels)
+    state = (labels._version, int(C))
+    hit = _label_checks.get(key)
+    if hit is not None and hit[0]() is labels and hit[1] == state:
+        return hit[2]
+    outside = (labels < 0) | (labels >= C)
+    ignored = False
+    if bool(outside.any()):
+        bad = outside & (labels != -100)
+        if bool(bad.any()):
+            y = int(labels[bad][0])
+            raise IndexError(f"Target {y} is out of bounds (classes: {C}, ignore_index: -100)")
+        ignored = True
+    if len(_label_checks) > 64:
+        _label_checks.clear()
+    _label_checks[key] = (weakref.ref(labels, lambda r, key=key: _forget_label_check(r, key)),
+                          state, ignored)
+    return ignored
+
+
+def _is_number(x):
+    return isinstance(x, (int, float)) and not isinstance(x, bool)
+
+
+class Adam(torch.optim.Adam):
+    """torch.optim.Adam whose step() and whole training loop run on the HIP
+    kernels (sgc_adam_step_f32, sgc_train_adam_f32; the arithmetic and its
+    operation order: include/sgc_amd.h).
+
+    step(closure=None) takes the device path -- one launch per param group,
+    state["step"] advanced on the host as torch's non-capturable path does --
+    when, in every group, each parameter with a gradient is a contiguous
+    float32 tensor on one ROCm device with a dense float32 gradient, there are
+    at most 16 of them, amsgrad / maximize / capturable / differentiable /
+    fused / decoupled_weight_decay are off, and lr and the betas are Python
+    numbers.  Anything else is torch.optim.Adam.step itself, bit for bit (CPU
+    tensors: the reference's --no-cuda mode).
+
+    run_epochs(model, features, labels, epochs) is the loop of
+    citation.py:44-50 in one host call; see the method.
+
+    Device results are tolerance-equal to torch's (not bit-equal) and bitwise
+    reproducible run to run.
+    """
+
+    # -- step -----------------------------------------------------------------------
+    @staticmethod
+    def _group_plain(group):
+        return not (group["amsgrad"] or group["maximize"] or group["capturable"] or
+                    group["differentiable"] or group["fused"] or
+                    group.get("decoupled_weight_decay", False)) and \
+            _is_number(group["lr"]) and all(_is_number(b) for b in group["betas"]) and \
+            _is_number(group["eps"]) and _is_number(group["weight_decay"])
+
+    def _device_group(self, group):
+        """The group's parameters with a gradient when the group can take the
+        device path, else None."""
+        if not self._group_plain(group):
+            return None
+        ps = [p for p in group["params"] if p.grad is not None]
+        if len(ps) > MAX_TENSORS:
+            return None
+        dev = None
+        for p in ps:
+            g = p.grad
+            if (p.device.type != "cuda" or p.dtype != torch.float32 or not p.is_contiguous() or
+                    g.is_sparse or g.layout != torch.strided or g.dtype != torch.float32 or
+                    g.device != p.device or not g.is_contiguous() or
+                    (dev is not None and p.device != dev)):
+                return None
+            dev = p.device
+            st = self.state.get(p)
+            if st:
+                if (st["step"].device.type != "cpu" or not st["exp_avg"].is_contiguous() or
+                        not st["exp_avg_sq"].is_contiguous() or
+                        st["exp_avg"].dtype != torch.float32 or
+                        st["exp_avg_sq"].dtype != torch.float32):
+                    return None
+        return ps
+
+    def _init_state(self, p):
+        """torch's lazy state initialisation (Adam._init_group, the
+        non-capturable, non-fused form: the step count lives on the host)."""
+        st = self.state[p]
+        if len(st) == 0:
+            st["step"] = torch.tensor(0.0, dtype=torch.float64 if torch.get_default_dtype() ==
+                                      torch.float64 else torch.float32)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return st
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        plans = [self._device_group(g) for g in self.param_groups]
+        if any(ps is None for ps in plans):
+            return super().step(closure)
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+            plans = [self._device_group(g) for g in self.param_groups]  # the closure's gradients
+            if any(ps is None for ps in plans):
+                # (the closure has run: torch's step takes its gradients as they are)
+                super().step(None)
+                return loss
+        if not any(plans):  # no parameter has a gradient: nothing moves (as torch)
+            return loss
+        lib = _lib.load()
+        for group, ps in zip(self.param_groups, plans):
+            if not ps:
+                continue
+            states = [self._init_state(p) for p in ps]
+            dev = ps[0].device
+            nt = len(ps)
+            b1, b2 = group["betas"]
+            # one launch per run of parameters that share a step count (as a
+            # rule all of them: one launch)
+            steps = [int(st["step"].tolist()) + 1 for st in states]
+            for step in sorted(set(steps)):
+                idx = [i for i in range(nt) if steps[i] == step]
+                n = len(idx)
+                arr = lambda xs: (ctypes.c_void_p * n)(*xs)  # noqa: E731
+                with torch.cuda.device(dev):
+                    _lib.check(lib.sgc_adam_step_f32(
+                        n, arr([ps[i].data_ptr() for i in idx]),
+                        arr([ps[i].grad.data_ptr() for i in idx]),
+                        arr([states[i]["exp_avg"].data_ptr() for i in idx]),
+                        arr([states[i]["exp_avg_sq"].data_ptr() for i in idx]),
+                        (ctypes.c_int64 * n)(*[ps[i].numel() for i in idx]), step,
+                        float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                        float(group["weight_decay"]), _lib.stream_handle(dev)), "adam_step_f32")
+            for st in states:
+                st["step"] += 1
+        return loss
+
+    # -- the whole loop ---------------------------------------------------------------
+    def _fused_plan(self, model, features, labels):
+        """(W, b) when run_epochs can run as one sgc_train_adam_f32 call."""
+        from .models import SGC
+        if type(model) is not SGC or model.W.bias is None or len(self.param_groups) != 1:
+            return None
+        group = self.param_groups[0]
+        W, b = model.W.weight, model.W.bias
+        ps = group["params"]
+        if len(ps) != 2 or not ((ps[0] is W and ps[1] is b) or (ps[0] is b and ps[1] is W)):
+            return None
+        if not self._group_plain(group):
+            return None
+        x, y = features, labels
+        if not (isinstance(x, torch.Tensor) and x.device.type == "cuda" and
+                x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 1 and
+                x.shape[1] == W.shape[1] and 1 <= W.shape[0] <= 64):
+            return None
+        if not (isinstance(y, torch.Tensor) and y.dtype == torch.int64 and y.device == x.device and
+                y.shape == (x.shape[0],)):
+            return None
+        for p in (W, b):
+            if (p.device != x.device or p.dtype != torch.float32 or not p.is_contiguous() or
+                    not p.requires_grad):
+                return None
+            st = self.state.get(p)
+            if st and (st["step"].device.type != "cpu" or not st["exp_avg"].is_contiguous() or
+                       not st["exp_avg_sq"].is_contiguous() or
+                       st["exp_avg"].dtype != torch.float32 or
+                       st["exp_avg_sq"].dtype != torch.float32):
+                return None
+        sw, sb = self.state.get(W), self.state.get(b)
+        if bool(sw) != bool(sb) or (sw and sw["step"].tolist() != sb["step"].tolist()):
+            return None
+        if _labels_have_ignored(y, W.shape[0]):
+            return None
+        return W, b
+
+    def run_epochs(self, model, features, labels, epochs, loss_trace=False):
+        """The training loop of citation.py:44-50 -- `epochs` times zero_grad,
+        F.cross_entropy(model(features), labels), backward, step -- on an
+        sgc_amd.models.SGC model whose two parameters form this optimiser's
+        one param group.  On ROCm float32 features with at most 64 classes it
+        is one call of sgc_train_adam_f32: no launch is issued from Python per
+        epoch and, after the labels' one range check (once per labels tensor
+        object and version), nothing synchronises with the host.
+
+        Returns the last epoch's loss (the mean cross-entropy at the weights
+        before that epoch's update, what the reference's loop computes last)
+        as a 0-d tensor, or the [epochs] trace with loss_trace=True; None when
+        epochs == 0 (nothing is touched).
+
+        Afterwards the weights, exp_avg, exp_avg_sq and step (advanced by
+        `epochs`) are the state `epochs` calls of step() would have left, so a
+        later step() or run_epochs() continues from there.  The fused loop
+        forms no gradient tensors: the parameters' .grad is left None.
+
+        Everything else -- CPU tensors, 16-bit features, more than 64 classes,
+        a bias-free or foreign model, a param group step() would hand to
+        torch, rows labelled -100 -- runs the literal Python loop with
+        self.step() (on the CPU bit-equal to torch.optim.Adam driving the same
+        loop).  A label outside [0, C) other than -100 raises IndexError."""
+        epochs = int(epochs)
+        if epochs < 0:
+            raise ValueError(f"epochs must be >= 0, got {epochs}")
+        if epochs == 0:
+            return None
+        plan = self._fused_plan(model, features, labels)
+        if plan is None:
+            losses = []
+            for _ in range(epochs):
+                model.train()
+                self.zero_grad()
+                loss = F.cross_entropy(model(features), labels)
+                loss.backward()
+                self.step()
+                losses.append(loss.detach())
+            return torch.stack(losses) if loss_trace else losses[-1]
+        W, b = plan
+        model.train()
+        self.zero_grad(set_to_none=True)
+        group = self.param_groups[0]
+        x = features.detach()
+        if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+            x = x.contiguous()
+        y = labels.contiguous()
+        M, K = x.shape
+        C = W.shape[0]
+        dev = x.device
+        sw, sb = self._init_state(W), self._init_state(b)
+        step0 = int(sw["step"].tolist())
+        lib = _lib.load()
+        ws_bytes = lib.sgc_train_adam_workspace(M, K, C)
+        ws = getattr(self, "_train_ws", None)
+        if ws is None or ws.numel() < ws_bytes or ws.device != dev:
+            ws = self._train_ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=dev)
+        trace = torch.empty(epochs, dtype=torch.float32, device=dev)
+        b1, b2 = group["betas"]
+        with torch.no_grad(), torch.cuda.device(dev):
+            _lib.check(lib.sgc_train_adam_f32(
+                _lib.ptr(x), x.stride(0), _lib.ptr(W), _lib.ptr(b), _lib.ptr(y), M, K, C,
+                _lib.ptr(sw["exp_avg"]), _lib.ptr(sw["exp_avg_sq"]), _lib.ptr(sb["exp_avg"]),
+                _lib.ptr(sb["exp_avg_sq"]), step0, epochs, float(group["lr"]), float(b1),
+                float(b2), float(group["eps"]), float(group["weight_decay"]), _lib.ptr(trace),
+                _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)), "train_adam_f32")
+        for st in (sw, sb):
+            st["step"] += epochs
+        return trace if loss_trace else trace[-1]
