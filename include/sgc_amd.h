@@ -870,6 +870,17 @@ int sgc_plan_sorted_ex2(const int32_t *row_ptr, int64_t row_begin, int64_t row_e
  * nonzero; short rows are most rows and few nonzeros, and a whole row in
  * group 0 is that row's CSR chain in one launch, so the bits are the same.
  * Same layout and workspace; sgc_csr_colsplit is whole_rows = 0.
+ * sgc_csr_colsplit_ex2, coarse_rows = H >= T and coarse_groups = Gc >= 1
+ * dividing G: the rows above T are cut by length class.  A row of more than H
+ * nonzeros is cut at all G cuts.  A row of T+1..H nonzeros is cut only at the
+ * Gc coarse cuts -- coarse cut j is cuts[j * (G / Gc)] -- and the run of its
+ * coarse range j is stored in group j * (G / Gc); every other group holds
+ * nothing of it.  Long rows hold most nonzeros in few rows, so the fine cut
+ * (a smaller live X slice per launch) costs them almost nothing per row; a
+ * medium row keeps runs long enough to pay for its wave.  Each row's runs
+ * still come in ascending group order, each contiguous: the same bits.  Same
+ * layout and workspace; sgc_csr_colsplit_ex is Gc = G (H is then unused).
+ * SGC_EINVAL (nothing launched) when Gc < 1, Gc does not divide G or H < T.
  * ------------------------------------------------------------------------- */
 int64_t sgc_colsplit_workspace(int64_t n_rows, int32_t groups);
 int sgc_csr_colsplit(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
@@ -881,6 +892,11 @@ int sgc_csr_colsplit_ex(const int32_t *row_ptr, const int32_t *col_idx, const fl
                         const int32_t *cuts_host, int32_t whole_rows, int32_t *row_ptrs,
                         int32_t *col_out, float *val_out, void *workspace,
                         int64_t workspace_bytes, void *stream);
+int sgc_csr_colsplit_ex2(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
+                         int64_t n_rows, int64_t n_cols, int32_t groups,
+                         const int32_t *cuts_host, int32_t whole_rows, int32_t coarse_rows,
+                         int32_t coarse_groups, int32_t *row_ptrs, int32_t *col_out,
+                         float *val_out, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
  * One process, several GPUs (the multi-GPU form of the one

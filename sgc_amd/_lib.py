@@ -111,6 +111,8 @@ SIGNATURES = {
                                         _p]),
     "sgc_csr_colsplit_ex": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i32, _p, _i32, _p, _p, _p, _p,
                                            _i64, _p]),
+    "sgc_csr_colsplit_ex2": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i32, _p, _i32, _i32, _i32, _p,
+                                            _p, _p, _p, _i64, _p]),
     "sgc_plan_sorted_workspace": (_i64, [_i64]),
     "sgc_plan_sorted": (ctypes.c_int, [_p, _i64, _i64, _i32, _i32, _p, _p, _i64, _p, _p]),
     "sgc_plan_sorted_ex": (ctypes.c_int, [_p, _i64, _i64, _i32, _i32, _p, _p, _i64, _p, _p]),

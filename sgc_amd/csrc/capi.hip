@@ -136,6 +136,11 @@ int colsplit_ex(const int32_t *row_ptr, const int32_t *col_idx, const float *val
                 int64_t n_cols, int32_t groups, const int32_t *cuts_host, int32_t whole_rows,
                 int32_t *row_ptrs, int32_t *col_out, float *val_out, void *workspace,
                 int64_t workspace_bytes, hipStream_t stream);
+int colsplit_ex2(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
+                 int64_t n_rows, int64_t n_cols, int32_t groups, const int32_t *cuts_host,
+                 int32_t whole_rows, int32_t coarse_rows, int32_t coarse_groups,
+                 int32_t *row_ptrs, int32_t *col_out, float *val_out, void *workspace,
+                 int64_t workspace_bytes, hipStream_t stream);
 int mgpu_init(int ndev, const int *devices);
 int mgpu_finalize();
 int mgpu_attach(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n,
@@ -905,6 +910,16 @@ int sgc_csr_colsplit_ex(const int32_t *row_ptr, const int32_t *col_idx, const fl
                         void *workspace, int64_t workspace_bytes, void *stream) {
     return colsplit_ex(row_ptr, col_idx, val, n_rows, n_cols, groups, cuts_host, whole_rows,
                        row_ptrs, col_out, val_out, workspace, workspace_bytes, as_stream(stream));
+}
+
+int sgc_csr_colsplit_ex2(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
+                         int64_t n_rows, int64_t n_cols, int32_t groups,
+                         const int32_t *cuts_host, int32_t whole_rows, int32_t coarse_rows,
+                         int32_t coarse_groups, int32_t *row_ptrs, int32_t *col_out,
+                         float *val_out, void *workspace, int64_t workspace_bytes, void *stream) {
+    return colsplit_ex2(row_ptr, col_idx, val, n_rows, n_cols, groups, cuts_host, whole_rows,
+                        coarse_rows, coarse_groups, row_ptrs, col_out, val_out, workspace,
+                        workspace_bytes, as_stream(stream));
 }
 
 int64_t sgc_plan_sorted_workspace(int64_t n_rows) { return plan_sorted_workspace(n_rows); }

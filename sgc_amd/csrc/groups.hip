@@ -30,6 +30,23 @@
 // 7.98 -> 7.60; RMAT shape, G = 4, the K = 3 step 88.2 -> 85.6 ms.  The
 // Python layer's rule is T = 32 (propagate.GROUP_WHOLE_ROWS_RULE); the
 // multi-device engine's split (mgpu.hip) stays at T = 0.
+//
+// Length ladder (colsplit_ex2, coarse_rows = H, coarse_groups = Gc dividing G):
+// the rows above T come in two classes.  A medium row (T < length <= H) is cut
+// only at the Gc coarse cuts -- coarse cut j is fine cut j * (G / Gc) -- and
+// the run of its coarse range j is stored in fine group j * (G / Gc); it is
+// empty in every other group.  A heavy row (length > H) is cut at all G cuts.
+// Heavy rows hold most nonzeros in few rows with long runs, so they take a
+// fine cut (a smaller live X slice per launch) at almost no per-row cost,
+// while a medium row cut that fine would be runs of a few nonzeros each.  The
+// runs still come in ascending group order, each contiguous: every row's
+// chain over groups 0..G-1 is its CSR chain.  Gc = G is colsplit_ex.
+// Measured (interleaved, bit-identical, profiles/group_ladder/): RMAT shape,
+// the K = 3 step 85.45 -> 80.38 ms at (G, Gc, H) = (8, 4, 512); Reddit shape,
+// the K = 2 step 6.93 -> 6.77 ms at (4, 2, 64), while cutting only its rows
+// above 512 finer loses (7.07 .. 7.60 ms).  The Python layer's rule is
+// propagate.GROUP_LADDER_RULE; column_groups_rule below and the callers that
+// split S by it keep the size rule's G for every row above T.
 #include "common.h"
 
 #include <algorithm>
@@ -57,10 +74,18 @@ __device__ __forceinline__ int32_t lower_bound(const int32_t *__restrict__ col, 
     return lo;
 }
 
+// The row's class as the stride of the cuts it takes: G for a whole row (no
+// cut), G / Gc for a medium row (the coarse cuts), 1 for a heavy row.
+__device__ __forceinline__ int row_step(int32_t len, int G, int32_t whole_rows,
+                                        int32_t coarse_rows, int coarse_step) {
+    return len <= whole_rows ? G : len <= coarse_rows ? coarse_step : 1;
+}
+
 // per-row counts of every group (counts[g * n + r]) and per-block totals
 __global__ void colsplit_count_kernel(const int32_t *__restrict__ row_ptr,
                                       const int32_t *__restrict__ col, int32_t n, int32_t chunk,
                                       int G, Cuts cuts, int32_t whole_rows,
+                                      int32_t coarse_rows, int coarse_step,
                                       int32_t *__restrict__ counts,
                                       int32_t *__restrict__ block_sums) {
     __shared__ int32_t s_sum[kGroupsMax];
@@ -70,11 +95,13 @@ __global__ void colsplit_count_kernel(const int32_t *__restrict__ row_ptr,
     int32_t mine[kGroupsMax] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int32_t r = r0 + threadIdx.x; r < r1; r += blockDim.x) {
         const int32_t k0 = row_ptr[r], k1 = row_ptr[r + 1];
-        const bool whole = k1 - k0 <= whole_rows;  // a short row stays in group 0
+        // cuts taken: every `step`-th (a short row none: it stays in group 0)
+        const int step = row_step(k1 - k0, G, whole_rows, coarse_rows, coarse_step);
         int32_t lo = k0;
         for (int g = 0; g < G; ++g) {
-            const int32_t hi =
-                (whole || g + 1 == G) ? k1 : lower_bound(col, lo, k1, cuts.c[g + 1]);
+            int32_t hi = lo;  // a group between two of the row's cuts: empty
+            if (g % step == 0)
+                hi = g + step >= G ? k1 : lower_bound(col, lo, k1, cuts.c[g + step]);
             counts[(int64_t)g * n + r] = hi - lo;
             mine[g] += hi - lo;
             lo = hi;
@@ -140,7 +167,8 @@ __global__ void colsplit_rowptr_kernel(const int32_t *__restrict__ counts, int32
 __global__ void colsplit_fill_kernel(const int32_t *__restrict__ row_ptr,
                                      const int32_t *__restrict__ col,
                                      const float *__restrict__ val, int32_t n, int G, Cuts cuts,
-                                     int32_t whole_rows, const int32_t *__restrict__ row_ptrs,
+                                     int32_t whole_rows, int32_t coarse_rows, int coarse_step,
+                                     const int32_t *__restrict__ row_ptrs,
                                      int32_t *__restrict__ col_out, float *__restrict__ val_out) {
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t waves = (int64_t)gridDim.x * (blockDim.x / kWave);
@@ -155,9 +183,11 @@ __global__ void colsplit_fill_kernel(const int32_t *__restrict__ row_ptr,
             }
             continue;
         }
+        // wave-uniform too: the row's cuts are every `step`-th
+        const int step = row_step(k1 - k0, G, whole_rows, coarse_rows, coarse_step);
         int32_t lo = k0;
-        for (int g = 0; g < G; ++g) {
-            const int32_t hi = (g + 1 == G) ? k1 : lower_bound(col, lo, k1, cuts.c[g + 1]);
+        for (int g = 0; g < G; g += step) {
+            const int32_t hi = g + step >= G ? k1 : lower_bound(col, lo, k1, cuts.c[g + step]);
             const int32_t dst = row_ptrs[(int64_t)g * (n + 1) + r];
             for (int32_t k = lo + lane; k < hi; k += kWave) {
                 col_out[dst + (k - lo)] = col[k];
@@ -181,13 +211,18 @@ int64_t colsplit_workspace(int64_t n_rows, int32_t groups) {
                      up((size_t)groups * nblocks(n_rows) * sizeof(int32_t)));
 }
 
-int colsplit_ex(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n_rows,
-                int64_t n_cols, int32_t groups, const int32_t *cuts_host, int32_t whole_rows,
-                int32_t *row_ptrs, int32_t *col_out, float *val_out, void *workspace,
-                int64_t workspace_bytes, hipStream_t stream) {
+int colsplit_ex2(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
+                 int64_t n_rows, int64_t n_cols, int32_t groups, const int32_t *cuts_host,
+                 int32_t whole_rows, int32_t coarse_rows, int32_t coarse_groups,
+                 int32_t *row_ptrs, int32_t *col_out, float *val_out, void *workspace,
+                 int64_t workspace_bytes, hipStream_t stream) {
     SGC_REQUIRE(whole_rows >= 0, SGC_EINVAL, "colsplit: whole_rows must be >= 0");
     SGC_REQUIRE(groups >= 1 && groups <= kGroupsMax, SGC_EINVAL,
                 "colsplit: groups must be 1..%d", kGroupsMax);
+    SGC_REQUIRE(coarse_groups >= 1 && groups % coarse_groups == 0, SGC_EINVAL,
+                "colsplit: coarse_groups %d must divide groups %d", coarse_groups, groups);
+    SGC_REQUIRE(coarse_rows >= whole_rows, SGC_EINVAL,
+                "colsplit: coarse_rows %d < whole_rows %d", coarse_rows, whole_rows);
     SGC_REQUIRE(n_rows >= 0 && n_rows < INT32_MAX && n_cols >= 0 && n_cols < INT32_MAX,
                 SGC_ERANGE, "colsplit: bad shape");
     SGC_REQUIRE(row_ptr && row_ptrs && cuts_host && workspace, SGC_EINVAL,
@@ -210,6 +245,7 @@ int colsplit_ex(const int32_t *row_ptr, const int32_t *col_idx, const float *val
                 (long long)colsplit_workspace(n_rows, groups));
     SGC_REQUIRE(col_out && val_out, SGC_EINVAL, "colsplit: null output");
     const int32_t n = (int32_t)n_rows;
+    const int coarse_step = (int)(groups / coarse_groups);  // fine cuts per coarse cut
     const int nblk = nblocks(n_rows);
     const int32_t chunk = (int32_t)((n_rows + nblk - 1) / nblk);
     char *w = static_cast<char *>(workspace);
@@ -217,7 +253,8 @@ int colsplit_ex(const int32_t *row_ptr, const int32_t *col_idx, const float *val
     w += up((size_t)groups * n_rows * sizeof(int32_t));
     int32_t *block_sums = reinterpret_cast<int32_t *>(w);
     hipLaunchKernelGGL(colsplit_count_kernel, dim3(nblk), dim3(kThreads), 0, stream, row_ptr,
-                       col_idx, n, chunk, (int)groups, cuts, whole_rows, counts, block_sums);
+                       col_idx, n, chunk, (int)groups, cuts, whole_rows, coarse_rows, coarse_step,
+                       counts, block_sums);
     SGC_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(colsplit_scan_blocks_kernel, dim3(1), dim3(kWave), 0, stream, block_sums,
                        nblk, (int)groups);
@@ -227,9 +264,20 @@ int colsplit_ex(const int32_t *row_ptr, const int32_t *col_idx, const float *val
     SGC_HIP_CHECK(hipGetLastError());
     const int fill_blocks = (int)std::min<int64_t>((n_rows + 3) / 4, 8192);
     hipLaunchKernelGGL(colsplit_fill_kernel, dim3(fill_blocks), dim3(kThreads), 0, stream, row_ptr,
-                       col_idx, val, n, (int)groups, cuts, whole_rows, row_ptrs, col_out, val_out);
+                       col_idx, val, n, (int)groups, cuts, whole_rows, coarse_rows, coarse_step, row_ptrs,
+                       col_out, val_out);
     SGC_HIP_CHECK(hipGetLastError());
     return SGC_OK;
+}
+
+// every row above whole_rows cut at all the cuts (coarse_groups = groups)
+int colsplit_ex(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n_rows,
+                int64_t n_cols, int32_t groups, const int32_t *cuts_host, int32_t whole_rows,
+                int32_t *row_ptrs, int32_t *col_out, float *val_out, void *workspace,
+                int64_t workspace_bytes, hipStream_t stream) {
+    return colsplit_ex2(row_ptr, col_idx, val, n_rows, n_cols, groups, cuts_host, whole_rows,
+                        whole_rows, groups, row_ptrs, col_out, val_out, workspace,
+                        workspace_bytes, stream);
 }
 
 // the pure split: every row cut at the column cuts (whole_rows = 0)
@@ -276,7 +324,8 @@ int csr_cols_ascending(const int32_t *row_ptr, const int32_t *col_idx, int64_t n
     return SGC_OK;
 }
 
-// The size rule of sgc_amd/propagate.py column_groups_for (measured,
+// The size rule of sgc_amd/propagate.py (_size_rule_groups; its length
+// ladder, group_ladder_for, is the Python layer's alone) (measured,
 // DESIGN.md 4.2): G = 1 below 4 M nonzeros, under 128 features or at 129-256
 // (the one-row kernel's single slice); 4 from 64 M nonzeros; else 2.
 // SGC_AMD_COLUMN_GROUPS=G forces G, as in the Python layer.

@@ -184,6 +184,41 @@ GROUPS_WIDE_NNZ = 1 << 26   # from here four groups (RMAT shape)
 _WHOLE_ENV = os.environ.get("SGC_AMD_GROUP_WHOLE_ROWS")
 GROUP_WHOLE_ROWS = int(_WHOLE_ENV) if _WHOLE_ENV else None
 GROUP_WHOLE_ROWS_RULE = 32
+# Length ladder (sgc_csr_colsplit_ex2): the rows above T in two classes.  A
+# heavy row (more than H nonzeros) is cut at all G column cuts; a medium row
+# (T+1..H) only at the Gc coarse cuts (coarse cut j = fine cut j * G / Gc, its
+# run stored in fine group j * G / Gc), so it keeps the runs it has today.
+# Same bits.  Measured interleaved, every point bit-identical
+# (scripts/group_ladder_ab.py, profiles/group_ladder/), T = 32 throughout:
+# RMAT shape (F = 256, the one-row kernel), the K = 3 step at G = 4 uncut by
+# class 85.45 ms; (G, Gc) = (8, 4) at H = 256 / 512 / 1024 / 2048: 80.39 /
+# 80.38 / 83.74 / 89.16 -- the rows above 512 hold the nonzeros worth a finer
+# cut, the plateau is 256..512, the rule takes H = 512.
+# Reddit shape, the K = 2 step at 602 floats, G = 2 uncut by class 6.93 ms: the
+# fine cut of the heavy rows alone LOSES -- (G, Gc, H) = (4, 2, 512) 7.13,
+# (6, 2, 512) 7.07, (8, 2, 512) 7.15, (8, 2, 1024) 7.50, (3, 1, 512) 7.60,
+# (6, 3, 512) 7.15, (8, 4, 512) 7.28; T = 16 / 64 move these by < 0.1.  A launch
+# of 12.5 K heavy rows' runs alone is too short to fill the device, and the
+# medium rows gain from the finer cut as well: (4, 2, 128) 6.79, (4, 2, 64)
+# 6.77, every row above T cut four ways 6.77 (T = 16: 6.85, T = 64: 6.83),
+# eight ways 7.10.  So at this shape the ladder's gain is the four-way cut of
+# the rows above 64 (H = 64: the 15 K rows of 33..64 nonzeros keep runs of
+# ~24 instead of ~12 at no cost in time); one hop at 304 floats it loses (1.94
+# -> 2.01 ms; four ways uncut by class 1.98): a launch's fixed cost against a
+# gain that grows with nnz x width.  Break-even by those two widths is about
+# nnz x width = 9.4e9; the rule asks for GROUP_LADDER_MIN_WORK (1.18e10,
+# Reddit shape at 602 floats is 1.41e10).
+# GROUP_LADDER_RULE: the size rule's G (which stays the medium rows' Gc) ->
+# (G, H).  SGC_AMD_GROUP_COARSE_GROUPS=Gc / SGC_AMD_GROUP_COARSE_ROWS=H force
+# the two (Gc = G: no ladder); a forced SGC_AMD_COLUMN_GROUPS has no ladder
+# unless Gc is forced too.
+_COARSE_GROUPS_ENV = os.environ.get("SGC_AMD_GROUP_COARSE_GROUPS")
+GROUP_COARSE_GROUPS = int(_COARSE_GROUPS_ENV) if _COARSE_GROUPS_ENV else None
+_COARSE_ROWS_ENV = os.environ.get("SGC_AMD_GROUP_COARSE_ROWS")
+GROUP_COARSE_ROWS = int(_COARSE_ROWS_ENV) if _COARSE_ROWS_ENV else None
+GROUP_COARSE_ROWS_RULE = 512
+GROUP_LADDER_RULE = {2: (4, 64), 4: (8, 512)}  # the size rule's G (= Gc) -> (fine G, H)
+GROUP_LADDER_MIN_WORK = 11 << 30  # nnz x width below which Gc = 2 keeps G = 2
 
 
 def group_whole_rows_for(csr, G):
@@ -195,12 +230,9 @@ def group_whole_rows_for(csr, G):
     return GROUP_WHOLE_ROWS_RULE
 
 
-def column_groups_for(csr, width):
-    """Column groups for a plain launch of `width` features over `csr`."""
-    if csr.device.type != "cuda" or not csr.cols_ascending or csr.nnz == 0:
-        return 1
-    if COLUMN_GROUPS is not None:
-        return max(1, min(8, int(COLUMN_GROUPS), max(1, csr.n_cols)))
+def _size_rule_groups(csr, width):
+    """The size rule's coarse cut: the column groups every row above T had
+    before the length ladder (and the medium rows still have)."""
     if width < GROUPS_MIN_WIDTH or csr.nnz < GROUPS_MIN_NNZ:
         return 1
     if csr.nnz >= GROUPS_WIDE_NNZ:
@@ -208,6 +240,51 @@ def column_groups_for(csr, width):
     if 128 < width <= 256:  # the one-row kernel's single 256-float slice: no gain
         return 1            # (152 floats 1.56 -> 1.58 ms, 256 1.85 -> 1.88 at G = 2)
     return 2
+
+
+def group_coarse_for(csr, G):
+    """(Gc, H) of the length ladder for G column groups of `csr`: rows of more
+    than H nonzeros are cut at all G cuts, rows of T+1..H at the Gc coarse
+    ones.  Gc == G: no ladder.  A forced G (COLUMN_GROUPS) has no ladder unless
+    GROUP_COARSE_GROUPS asks for one; a Gc that does not divide G is ignored."""
+    T = group_whole_rows_for(csr, G)
+    if G <= 1:
+        return 1, 0
+    Gc, H = G, GROUP_COARSE_ROWS_RULE
+    if COLUMN_GROUPS is None:  # the rule's G: its coarse cut is the size rule's
+        coarse = 4 if csr.nnz >= GROUPS_WIDE_NNZ else 2
+        fine, rows = GROUP_LADDER_RULE.get(coarse, (coarse, H))
+        if fine == G:
+            Gc, H = coarse, rows
+    if GROUP_COARSE_GROUPS is not None and G % max(1, int(GROUP_COARSE_GROUPS)) == 0:
+        Gc = max(1, int(GROUP_COARSE_GROUPS))
+    if GROUP_COARSE_ROWS is not None:
+        H = int(GROUP_COARSE_ROWS)
+    return (Gc, max(H, T)) if Gc != G else (G, T)
+
+
+def group_ladder_for(csr, width):
+    """(G, Gc, H) for a plain launch of `width` features over `csr`: G column
+    groups, of which rows of at most H nonzeros take only the Gc coarse cuts
+    (Gc == G: every row above T is cut alike, H unused)."""
+    if csr.device.type != "cuda" or not csr.cols_ascending or csr.nnz == 0:
+        return 1, 1, 0
+    if COLUMN_GROUPS is not None:
+        G = max(1, min(8, int(COLUMN_GROUPS), max(1, csr.n_cols)))
+    else:
+        G = _size_rule_groups(csr, width)
+        # the ladder where it was measured to win: the one-row kernel's
+        # widths at four coarse groups, enough work per launch at two
+        measured = {4: 128 < width <= 256, 2: csr.nnz * width >= GROUP_LADDER_MIN_WORK}
+        if measured.get(G):
+            G = GROUP_LADDER_RULE.get(G, (G,))[0]
+    return (G, *group_coarse_for(csr, G))
+
+
+def column_groups_for(csr, width):
+    """Column groups (launches per hop) for a plain launch of `width`
+    features over `csr`: the G of group_ladder_for."""
+    return group_ladder_for(csr, width)[0]
 
 
 def _host_cols_ascending(row_ptr, col_idx):
@@ -276,12 +353,15 @@ class DeviceCSR:
         """Column cuts of the G column groups: group g = columns [c_g, c_{g+1})."""
         return [(g * self.n_cols) // G for g in range(G + 1)]
 
-    def column_groups(self, G, whole_rows=0):
-        """The G column-group CSRs of this one (sgc_csr_colsplit_ex; cached):
+    def column_groups(self, G, whole_rows=0, coarse_rows=None, coarse_groups=None):
+        """The G column-group CSRs of this one (sgc_csr_colsplit_ex2; cached):
         columns cut at g * n_cols / G, every row's run of each group in its
         storage order; group g's row_ptr points into one shared col/val
         copy.  A row of at most `whole_rows` nonzeros is not cut: all of it
-        is in group 0 (0 = the pure split).  Rows must have ascending
+        is in group 0 (0 = the pure split).  With `coarse_groups` = Gc
+        dividing G, a row of at most `coarse_rows` nonzeros is cut only at
+        every (G / Gc)-th cut, its runs in groups 0, G / Gc, ... (None = G:
+        every cut row is cut at all the cuts).  Rows must have ascending
         columns."""
         if not self.cols_ascending:
             raise ValueError("sgc_amd: column groups need rows with ascending columns")
@@ -289,7 +369,18 @@ class DeviceCSR:
         if whole_rows < 0:
             raise ValueError("sgc_amd: whole_rows must be >= 0")
         whole_rows = min(whole_rows, 2 ** 31 - 1)
-        key = ("groups", int(G), whole_rows)
+        G = int(G)
+        coarse_groups = G if coarse_groups is None else int(coarse_groups)
+        if coarse_groups < 1 or G % coarse_groups:
+            raise ValueError(f"sgc_amd: coarse_groups {coarse_groups} must divide G = {G}")
+        if coarse_groups == G or coarse_rows is None:  # no medium class: one cache entry
+            coarse_groups, coarse_rows = G, whole_rows
+        coarse_rows = min(int(coarse_rows), 2 ** 31 - 1)
+        if coarse_rows < whole_rows:
+            raise ValueError("sgc_amd: coarse_rows must be >= whole_rows")
+        key = ("groups", G, whole_rows)
+        if coarse_groups != G:
+            key += (coarse_rows, coarse_groups)
         if key not in self._plans:
             import ctypes
             lib = _lib.load()
@@ -301,12 +392,14 @@ class DeviceCSR:
             ws_bytes = lib.sgc_colsplit_workspace(n, G)
             ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=dev)
             with torch.cuda.device(dev):
-                _lib.check(lib.sgc_csr_colsplit_ex(_lib.ptr(self.row_ptr), _lib.ptr(self.col_idx),
-                                                   _lib.ptr(self.val), n, self.n_cols, G,
-                                                   ctypes.cast(cuts, ctypes.c_void_p), whole_rows,
-                                                   _lib.ptr(row_ptrs), _lib.ptr(col),
-                                                   _lib.ptr(val), _lib.ptr(ws), ws_bytes,
-                                                   _lib.stream_handle(dev)), "csr_colsplit")
+                _lib.check(lib.sgc_csr_colsplit_ex2(_lib.ptr(self.row_ptr),
+                                                    _lib.ptr(self.col_idx), _lib.ptr(self.val), n,
+                                                    self.n_cols, G,
+                                                    ctypes.cast(cuts, ctypes.c_void_p), whole_rows,
+                                                    coarse_rows, coarse_groups,
+                                                    _lib.ptr(row_ptrs), _lib.ptr(col),
+                                                    _lib.ptr(val), _lib.ptr(ws), ws_bytes,
+                                                    _lib.stream_handle(dev)), "csr_colsplit")
             del ws  # stream-ordered: the allocator reuses it after the kernels
             self._plans[key] = [DeviceCSR(n, self.n_cols, row_ptrs[g], col[:nnz], val[:nnz],
                                           self.status) for g in range(G)]
@@ -322,7 +415,8 @@ class DeviceCSR:
 
     def drop_groups(self):
         """Free the cached column-group copies of S (and their plans): one
-        more col/val copy per (G, whole_rows) (188 MB at Reddit shape).  They
+        more col/val copy per (G, whole_rows, coarse_rows, coarse_groups) (188
+        MB at Reddit shape; propagate() under the rules uses one).  They
         are rebuilt on the next launch that uses them."""
         self.release_prepared()  # recorded launch lists hold the groups' pointers
         for key in [k for k in self._plans if isinstance(k, tuple) and k[:1] == ("groups",)]:
@@ -331,12 +425,14 @@ class DeviceCSR:
 
     def groups_or_self(self, G):
         """The G column-group CSRs under the whole-row rule
-        (group_whole_rows_for), or [self] when G == 1 or when the copy does
-        not fit in device memory (a schedule: the results are the same)."""
+        (group_whole_rows_for) and the length ladder (group_coarse_for), or
+        [self] when G == 1 or when the copy does not fit in device memory (a
+        schedule: the results are the same)."""
         if G <= 1:
             return [self]
         try:
-            return self.column_groups(G, group_whole_rows_for(self, G))
+            Gc, H = group_coarse_for(self, G)
+            return self.column_groups(G, group_whole_rows_for(self, G), H, Gc)
         except torch.cuda.OutOfMemoryError:
             return [self]
 
@@ -912,7 +1008,8 @@ def propagate(csr: DeviceCSR, X: torch.Tensor, K: int, out=None, use_plan=True, 
             and not torch.cuda.is_current_stream_capturing()):
         key = ("list", X.stride(0), F, int(K), out.stride(0), X.data_ptr() % 128 == 0,
                threshold, hub_threshold, bool(use_plan), G_rule,
-               group_whole_rows_for(csr, G_rule), stream, PAD_X0, wide_knob, wide_ts)
+               group_whole_rows_for(csr, G_rule), group_coarse_for(csr, G_rule), stream, PAD_X0,
+               wide_knob, wide_ts)
         prep = csr._plans.get(key)
         if prep is not None:
             rc = lib.sgc_launch_list_run(prep[1].handle, X.data_ptr(), out.data_ptr(), stream)
