@@ -50,6 +50,8 @@ def parse(argv=None):
                    help="use a seeded Reddit-shape synthetic graph with this many nodes (0: read data/)")
     p.add_argument("--device-lbfgs", action="store_true", default=False,
                    help="train with sgc_amd.optim.LBFGS (no host synchronisation per iteration)")
+    p.add_argument("--fused-lbfgs", action="store_true", default=False,
+                   help="train with sgc_amd.optim.LBFGS.run_steps (all steps in one host call)")
     p.add_argument("--feature-dtype", choices=sorted(FEATURE_DTYPES), default="float32",
                    help="storage type of the features: cast once after loading; the propagated "
                         "features, the training and the evaluation rows stay in it")
@@ -86,7 +88,14 @@ def synthetic_reddit(n, seed=0):
     return out
 
 
-def train_regression(model, train_features, train_labels, epochs, device_lbfgs=False):
+def train_regression(model, train_features, train_labels, epochs, device_lbfgs=False,
+                     fused_lbfgs=False):
+    if fused_lbfgs:  # every step, closures included, enqueued by one host call
+        from sgc_amd.optim import LBFGS
+        optimizer = LBFGS(model.parameters(), lr=1)
+        t = perf_counter()
+        optimizer.run_steps(model, train_features, train_labels, epochs)
+        return model, perf_counter() - t
     if device_lbfgs:  # the whole L-BFGS iteration on the GPU (sgc_amd/optim.py)
         from sgc_amd.optim import LBFGS
         optimizer = LBFGS(model.parameters(), lr=1)
@@ -132,7 +141,8 @@ def main(argv=None):
         train_features = processed[idx_train]
     test_features = processed[idx_test if args.test else idx_val]
     model, train_time = train_regression(model, train_features, labels[idx_train], args.epochs,
-                                         device_lbfgs=args.device_lbfgs)
+                                         device_lbfgs=args.device_lbfgs,
+                                         fused_lbfgs=args.fused_lbfgs)
     test_f1, _ = test_regression(model, test_features, labels[idx_test if args.test else idx_val])
     print("Total Time: {:.4f}s, {} F1: {:.4f}".format(train_time + precompute_time,
                                                       "Test" if args.test else "Val", test_f1))

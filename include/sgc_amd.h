@@ -721,6 +721,55 @@ int sgc_lbfgs_iterate_f32(void *state, int32_t n_tensors, float *const *param_pt
 int sgc_lbfgs_read_status(const void *state, int64_t *out_host, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Fused L-BFGS training: `steps` times optim.LBFGS(lr).step(closure) of
+ * reddit.py:51-64 for the SGC classifier z = X W^T + b, the closure
+ * F.cross_entropy(z, labels) plus backward on the device side too.
+ *
+ *   sgc_train_lbfgs_f32: one host call enqueues everything on `stream`: no
+ *     host synchronisation, no allocation, no atomics, every sum in a fixed
+ *     order.  Per step: the reset of sgc_lbfgs_begin_step, then max_iter times
+ *     [the closure: launches A and B of sgc_linear_xent_f32 and its two
+ *     reductions, writing loss, dW and db into a flat gradient (W then b) in
+ *     the workspace; then the launch of sgc_lbfgs_iterate_f32 on the tensors
+ *     W, b and that gradient], then a one-thread launch that copies the six
+ *     status words to status_trace.  Kernel selection is sgc_linear_xent_f32's
+ *     (alignment of X, ldx, K and W; "backward_kernel" and "tile_buffers").
+ *     The closure launches are stop-aware forms of sgc_linear_xent_f32's
+ *     kernels: each tests the state's stop word with one wave-uniform load at
+ *     entry and returns when it is set, so once a step has stopped its
+ *     remaining iterations cost empty launches and move nothing; while the
+ *     step runs they compute sgc_linear_xent_f32's bits.  The result -- W, b,
+ *     the whole state, every status and loss -- is therefore bit-identical to
+ *     the same steps driven closure by closure through sgc_linear_xent_f32 and
+ *     sgc_lbfgs_iterate_f32.
+ *     state: the sgc_lbfgs_workspace state, initialised by sgc_lbfgs_init with
+ *     n = C*K + C (n = C*K when b is NULL); the flat vector is W then b.  The
+ *     same state serves sgc_lbfgs_iterate_f32: fused and stepwise steps may
+ *     alternate.  W [C, K] and b [C] are updated in place.
+ *     loss_trace: `steps` device floats or NULL; loss_trace[s] is the loss of
+ *     step s's first closure (what step() returns).  status_trace: 6 * steps
+ *     device int64 or NULL; status_trace[6 s .. 6 s + 5] are the status words
+ *     of sgc_lbfgs_read_status as they stand at the end of step s.  The
+ *     caller copies the table back when it likes: the only read-back.
+ *     Limits: those of the parts -- C <= 64, n <= 65536, ldx >= K, X 4-B
+ *     aligned, the 31-bit offset limits of sgc_linear_xent_f32.  Labels must
+ *     lie in [0, C) (not checked on the device; the Python layer checks them).
+ *     steps == 0 returns SGC_OK and touches nothing.
+ *   sgc_train_lbfgs_workspace(M, K, C): bytes of `workspace` -- the flat
+ *     gradient, one loss float and sgc_linear_xent_workspace(M, K, C); 0 for an
+ *     empty shape, C > 64 or C*K > 65536.
+ * Argument errors return SGC_EINVAL / SGC_ERANGE / SGC_ENOMEM (workspace)
+ * with an sgc_last_error text before any device call.
+ * ------------------------------------------------------------------------- */
+int64_t sgc_train_lbfgs_workspace(int64_t M, int64_t K, int64_t C);
+int sgc_train_lbfgs_f32(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels,
+                        int64_t M, int64_t K, int64_t C, void *state, int32_t steps,
+                        double lr, int32_t max_iter, int32_t max_eval,
+                        double tolerance_grad, double tolerance_change,
+                        float *loss_trace, int64_t *status_trace,
+                        void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Device-resident Adam: optim.Adam of citation.py:41-50 (torch's default
  * single-tensor math: amsgrad=False, maximize=False, coupled L2 weight decay).
  *

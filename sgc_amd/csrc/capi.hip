@@ -155,6 +155,11 @@ int lbfgs_iterate(void *state, int32_t n_tensors, float *const *params, const fl
                   const int64_t *numels, const float *loss, double lr, int32_t max_iter,
                   int32_t max_eval, double tol_grad, double tol_change, hipStream_t s);
 int lbfgs_read_status(const void *state, int64_t *out_host, hipStream_t s);
+int64_t train_lbfgs_workspace(int64_t M, int64_t K, int64_t C);
+int train_lbfgs(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels, int64_t M,
+                int64_t K, int64_t C, void *state, int32_t steps, double lr, int32_t max_iter,
+                int32_t max_eval, double tol_grad, double tol_change, float *loss_trace,
+                int64_t *status_trace, void *ws, int64_t ws_bytes, hipStream_t s);
 extern int g_adam_kernel, g_adam_kernel_last;
 int adam_set_tuning(int64_t value);
 int64_t adam_small_max_rows();
@@ -772,6 +777,20 @@ int sgc_lbfgs_read_status(const void *state, int64_t *out_host, void *stream) {
     return lbfgs_read_status(state, out_host, as_stream(stream));
 }
 
+int64_t sgc_train_lbfgs_workspace(int64_t M, int64_t K, int64_t C) {
+    return train_lbfgs_workspace(M, K, C);
+}
+
+int sgc_train_lbfgs_f32(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels,
+                        int64_t M, int64_t K, int64_t C, void *state, int32_t steps, double lr,
+                        int32_t max_iter, int32_t max_eval, double tolerance_grad,
+                        double tolerance_change, float *loss_trace, int64_t *status_trace,
+                        void *workspace, int64_t workspace_bytes, void *stream) {
+    return train_lbfgs(X, ldx, W, b, labels, M, K, C, state, steps, lr, max_iter, max_eval,
+                       tolerance_grad, tolerance_change, loss_trace, status_trace, workspace,
+                       workspace_bytes, as_stream(stream));
+}
+
 int sgc_adam_step_f32(int32_t n_tensors, float *const *param_ptrs_host,
                       const float *const *grad_ptrs_host, float *const *exp_avg_ptrs_host,
                       float *const *exp_avg_sq_ptrs_host, const int64_t *numels_host, int64_t step,
@@ -811,6 +830,7 @@ int sgc_warmup(uint32_t units, void *stream) {
     if (units & SGC_WARM_CLASSIFIER) {
         SGC_HIP_CHECK(warm_linear(s));
         SGC_HIP_CHECK(warm_xent(s));
+        SGC_HIP_CHECK(warm_xent_fwd_stop(s));
         SGC_HIP_CHECK(warm_loss(s));
         SGC_HIP_CHECK(warm_lbfgs(s));
         SGC_HIP_CHECK(warm_adam(s));

@@ -52,6 +52,7 @@ hipError_t warm_groups(hipStream_t);
 hipError_t warm_exchange(hipStream_t);
 hipError_t warm_linear(hipStream_t);
 hipError_t warm_xent(hipStream_t);
+hipError_t warm_xent_fwd_stop(hipStream_t);
 hipError_t warm_loss(hipStream_t);
 hipError_t warm_lbfgs(hipStream_t);
 hipError_t warm_normalize(hipStream_t);

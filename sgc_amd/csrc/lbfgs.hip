@@ -433,6 +433,34 @@ void launch_iterate(char *state, const Tensors &T, const float *loss, float lr, 
                        max_iter, max_eval, tg, tc);
 }
 
+// the iterate launch for n parameters: the size class by 16-B chunks per thread
+hipError_t enqueue_iterate(char *st, const Tensors &T, int64_t n, const float *loss, float lrf,
+                           int max_iter, int max_eval, double tol_grad, double tol_change,
+                           hipStream_t s) {
+    const int64_t chunks = row_ld(n) / 4;
+    if (chunks <= 1 * kThreads)
+        launch_iterate<1>(st, T, loss, lrf, max_iter, max_eval, tol_grad, tol_change, s);
+    else if (chunks <= 2 * kThreads)
+        launch_iterate<2>(st, T, loss, lrf, max_iter, max_eval, tol_grad, tol_change, s);
+    else if (chunks <= 4 * kThreads)
+        launch_iterate<4>(st, T, loss, lrf, max_iter, max_eval, tol_grad, tol_change, s);
+    else if (chunks <= 8 * kThreads)
+        launch_iterate<8>(st, T, loss, lrf, max_iter, max_eval, tol_grad, tol_change, s);
+    else
+        launch_iterate<16>(st, T, loss, lrf, max_iter, max_eval, tol_grad, tol_change, s);
+    return hipGetLastError();
+}
+
+// sgc_train_lbfgs_f32's per-step snapshot: the six status words, one thread
+__global__ void lbfgs_snapshot_kernel(const Header *H, int64_t *out) {
+    out[0] = H->n_iter;
+    out[1] = H->func_evals;
+    out[2] = H->iters;
+    out[3] = H->evals;
+    out[4] = H->stop;
+    out[5] = H->hist_len;
+}
+
 }  // namespace
 
 static int check_shape(const char *what, int64_t n, int64_t history_size);
@@ -518,20 +546,8 @@ int lbfgs_iterate(void *state, int32_t n_tensors, float *const *params, const fl
         T.g[i] = grads[i];
     }
     SGC_REQUIRE(loss, SGC_EINVAL, "lbfgs_iterate: null loss");
-    char *st = reinterpret_cast<char *>(state);
-    const int64_t chunks = row_ld(n) / 4;
-    const float lrf = (float)lr;
-    if (chunks <= 1 * kThreads)
-        launch_iterate<1>(st, T, loss, lrf, max_iter, max_eval, tol_grad, tol_change, s);
-    else if (chunks <= 2 * kThreads)
-        launch_iterate<2>(st, T, loss, lrf, max_iter, max_eval, tol_grad, tol_change, s);
-    else if (chunks <= 4 * kThreads)
-        launch_iterate<4>(st, T, loss, lrf, max_iter, max_eval, tol_grad, tol_change, s);
-    else if (chunks <= 8 * kThreads)
-        launch_iterate<8>(st, T, loss, lrf, max_iter, max_eval, tol_grad, tol_change, s);
-    else
-        launch_iterate<16>(st, T, loss, lrf, max_iter, max_eval, tol_grad, tol_change, s);
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = enqueue_iterate(reinterpret_cast<char *>(state), T, n, loss, (float)lr,
+                                         max_iter, max_eval, tol_grad, tol_change, s);
     SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "lbfgs_iterate launch failed: %s", hipGetErrorString(e));
     return SGC_OK;
 }
@@ -541,6 +557,105 @@ int lbfgs_read_status(const void *state, int64_t *out_host, hipStream_t s) {
     SGC_REQUIRE(out_host, SGC_EINVAL, "lbfgs_read_status: null out_host");
     SGC_HIP_CHECK(hipMemcpyAsync(out_host, state, 6 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     SGC_HIP_CHECK(hipStreamSynchronize(s));
+    return SGC_OK;
+}
+
+// ---- sgc_train_lbfgs_f32: `steps` whole steps enqueued by one host call ------
+// The loop of reddit.py:51-64 for the SGC classifier with the closure on the
+// device side too: per step the reset of lbfgs_begin_step, then max_iter times
+// [the four launches of sgc_linear_xent_f32 behind the stop word (xent.hip),
+// lbfgs_iterate_kernel], then the status snapshot.  The closure writes loss,
+// dW and db into the workspace (the flat gradient, W then b), which the
+// iterate launch reads as its two gradient tensors.  Once an iterate launch has
+// set the stop word, the rest of the step's launches return at entry: nothing
+// moves until the next step's reset.  The first closure of step s runs always
+// (the reset precedes it) and writes its loss straight into loss_trace[s].
+int64_t xent_workspace_bytes(int64_t M, int64_t K, int64_t C);  // xent.hip
+int xent_closure_check(const char *what, int64_t M, int64_t K, int64_t C, int64_t ldx);
+int xent_closure(const int64_t *stop, const float *X, int64_t ldx, const float *W, const float *b,
+                 const int64_t *labels, int64_t M, int64_t K, int64_t C, float *loss, float *dW,
+                 float *db, void *ws, hipStream_t s);
+
+// workspace: gradient [n] | loss | the fused step's workspace, each 256-B aligned
+int64_t train_lbfgs_workspace(int64_t M, int64_t K, int64_t C) {
+    if (M <= 0 || K <= 0 || C <= 0 || C > 64 || C * K > kMaxN) return 0;
+    return 256 + round_up((C * K + C) * 4, 256) + 256 + xent_workspace_bytes(M, K, C);
+}
+
+int train_lbfgs(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels, int64_t M,
+                int64_t K, int64_t C, void *state, int32_t steps, double lr, int32_t max_iter,
+                int32_t max_eval, double tol_grad, double tol_change, float *loss_trace,
+                int64_t *status_trace, void *ws, int64_t ws_bytes, hipStream_t s) {
+    SGC_REQUIRE(steps >= 0, SGC_EINVAL, "train_lbfgs: steps=%d < 0", steps);
+    SGC_REQUIRE(M > 0 && K > 0 && C > 0 && C <= 64 && ldx >= K, SGC_EINVAL,
+                "train_lbfgs: bad shape M=%lld K=%lld C=%lld ldx=%lld (1 <= C <= 64, ldx >= K)",
+                (long long)M, (long long)K, (long long)C, (long long)ldx);
+    SGC_REQUIRE(max_iter >= 1, SGC_EINVAL, "train_lbfgs: max_iter=%d < 1", max_iter);
+    SGC_REQUIRE(X && W && labels && state && ws, SGC_EINVAL, "train_lbfgs: null pointer");
+    SGC_REQUIRE(reinterpret_cast<uintptr_t>(X) % 4 == 0, SGC_EINVAL,
+                "train_lbfgs: X not 4-B aligned");
+    const int64_t ck = C * K, n = ck + (b ? C : 0);
+    SGC_REQUIRE(n <= kMaxN, SGC_ERANGE, "train_lbfgs: n=%lld > %lld parameters", (long long)n,
+                (long long)kMaxN);
+    if (const int rc = xent_closure_check("train_lbfgs", M, K, C, ldx)) return rc;
+    const int64_t need = train_lbfgs_workspace(M, K, C);
+    SGC_REQUIRE(ws_bytes >= need, SGC_ENOMEM, "train_lbfgs: workspace %lld < %lld",
+                (long long)ws_bytes, (long long)need);
+    if (steps == 0) return SGC_OK;
+    {
+        std::lock_guard<std::mutex> lock(g_states_mu);
+        auto it = g_states.find(state);
+        SGC_REQUIRE(it != g_states.end(), SGC_EINVAL,
+                    "train_lbfgs: state not initialised by sgc_lbfgs_init");
+        SGC_REQUIRE(it->second.n == n, SGC_EINVAL,
+                    "train_lbfgs: C*K%s = %lld parameters, the state was initialised for n=%lld",
+                    b ? " + C" : "", (long long)n, (long long)it->second.n);
+    }
+    char *p = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
+    float *grad = reinterpret_cast<float *>(p);
+    p += round_up((ck + C) * 4, 256);
+    float *loss_slot = reinterpret_cast<float *>(p);
+    p += 256;
+    void *xent_ws = p;
+    Tensors T;
+    for (int i = 0; i < kMaxTensors; ++i) {
+        T.p[i] = nullptr;
+        T.g[i] = nullptr;
+    }
+    // (the table lbfgs_iterate builds for [W, b]: the same kernel arguments)
+    T.count = b ? 2 : 1;
+    T.p[0] = W;
+    T.g[0] = grad;
+    T.off[0] = 0;
+    if (b) {
+        T.p[1] = b;
+        T.g[1] = grad + ck;
+        T.off[1] = (int32_t)ck;
+    }
+    for (int i = T.count; i <= kMaxTensors; ++i) T.off[i] = (int32_t)n;
+    char *st = reinterpret_cast<char *>(state);
+    Header *H = reinterpret_cast<Header *>(state);
+    const int64_t *stop = &H->stop;  // (a device address: never read here)
+    const float lrf = (float)lr;
+    for (int32_t step = 0; step < steps; ++step) {
+        hipLaunchKernelGGL(lbfgs_begin_kernel, dim3(1), dim3(1), 0, s, H);
+        SGC_HIP_CHECK(hipGetLastError());
+        for (int32_t it = 0; it < max_iter; ++it) {
+            float *loss = (it == 0 && loss_trace) ? loss_trace + step : loss_slot;
+            if (const int rc = xent_closure(stop, X, ldx, W, b, labels, M, K, C, loss, grad,
+                                            b ? grad + ck : nullptr, xent_ws, s))
+                return rc;
+            const hipError_t e = enqueue_iterate(st, T, n, loss, lrf, max_iter, max_eval, tol_grad,
+                                                 tol_change, s);
+            SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "train_lbfgs launch failed: %s",
+                        hipGetErrorString(e));
+        }
+        if (status_trace) {
+            hipLaunchKernelGGL(lbfgs_snapshot_kernel, dim3(1), dim3(1), 0, s, H,
+                               status_trace + 6 * (int64_t)step);
+            SGC_HIP_CHECK(hipGetLastError());
+        }
+    }
     return SGC_OK;
 }
 

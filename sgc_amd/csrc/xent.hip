@@ -21,15 +21,40 @@
 //   C' xent_reduce_adam_kernel (sgc_train_adam_f32's general schedule, adam.hip)
 //                         both reductions of C in one launch, each finished
 //                         gradient element applied to W / b by Adam in place.
+//
+// Stop-aware forms (sgc_train_lbfgs_f32, lbfgs.hip): the kernels of A, B
+// (fp32 slabs and column blocks) and C exist a second time as
+// <name>_stop_kernel, which take the L-BFGS state's stop word as their first
+// argument, test it with one wave-uniform load at entry and return when it is
+// set.  They are compiled from the same text, with SGC_XENT_KERNEL /
+// _STOP_PARAM / _STOP_TEST naming the second form and only those kernels
+// visible: B and C when this file includes itself (SGC_XENT_STOP_PASS 2), A
+// when xent_fwd_stop.hip includes it (SGC_XENT_STOP_PASS 1: a unit of its
+// own, because a second set of A's kernels in this unit changed the register
+// allocation of the first).  Without SGC_XENT_STOP_PASS the three macros leave
+// the plain kernels' text as it was, so their device code does not change, and
+// the stop-aware bodies cannot drift from them.
+#ifndef SGC_XENT_STOP_PASS
 #include "adam_update.h"
 #include "gemm_tile.h"
 #include "split_bf16.h"
 
+#define SGC_XENT_KERNEL(name) name##_kernel
+#define SGC_XENT_STOP_PARAM
+#define SGC_XENT_STOP_TEST
+
 namespace sgc {
 
+// launch A behind the stop word: xent_fwd_stop_kernel<V, NT, g_tile_buffers> (xent_fwd_stop.hip)
+hipError_t launch_xent_fwd_stop(int V, int NT, const int64_t *stop, const float *X, int64_t ldx,
+                                const float *W, const float *b, const int64_t *labels, int M, int K,
+                                int C, float *G, int ldg, double *loss_part, float *db_part,
+                                float *logits, int64_t ldl, hipStream_t s);
 
 namespace {
 
+#endif  // !SGC_XENT_STOP_PASS
+#if !defined(SGC_XENT_STOP_PASS) || SGC_XENT_STOP_PASS == 1
 __device__ __forceinline__ float group16_max(float v) {
 #pragma unroll
     for (int m = 1; m < 16; m <<= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
@@ -43,12 +68,13 @@ __device__ __forceinline__ float group16_sum(float v) {
 
 // ---- A: logits -> G, loss / dG partials ------------------------------------
 template <int V, int NT, int NB>
-__global__ __launch_bounds__(256) void xent_fwd_kernel(
-    const float *__restrict__ X, int64_t ldx, const float *__restrict__ W,
+__global__ __launch_bounds__(256) void SGC_XENT_KERNEL(xent_fwd)(
+    SGC_XENT_STOP_PARAM const float *__restrict__ X, int64_t ldx, const float *__restrict__ W,
     const float *__restrict__ b, const int64_t *__restrict__ labels, int M, int K, int C,
     float inv_m, float *__restrict__ G, int ldg, double *__restrict__ loss_part,
     float *__restrict__ db_part, float *__restrict__ logits, int64_t ldl) {
     __shared__ LdsTile<V, NT, NB> sm;
+    SGC_XENT_STOP_TEST
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int wave = blockIdx.x * 4 + w;
     const int i = lane & 15, g = lane >> 4;
@@ -128,7 +154,9 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(
         if (g == 0) db_part[(int64_t)wave * ldg + n * 16 + i] = s;
     }
 }
+#endif  // pass 1
 
+#ifndef SGC_XENT_STOP_PASS
 #ifndef SGC_DW_SLABS
 #define SGC_DW_SLABS 512
 #endif
@@ -156,12 +184,14 @@ inline bool dw_slab_fits(int64_t rows_per, int64_t ldx, int64_t ldg) {
 // db_slab (nullable): wave 0's first column group also sums its block's G
 // rows per class (lane groups in row order, then across them) into
 // db_slab[blk][C16] -- db = sum_m G_m from the same loads, in a fixed order.
+#endif  // !SGC_XENT_STOP_PASS
+#if !defined(SGC_XENT_STOP_PASS) || SGC_XENT_STOP_PASS == 2
 template <int V, int NT, int CT>
-__global__ __launch_bounds__(256) void xent_dw_kernel(const float *__restrict__ X, int64_t ldx,
-                                                     const float *__restrict__ G, int ldg, int M,
-                                                     int K, int C, int rows_per,
-                                                     float *__restrict__ slab,
-                                                     float *__restrict__ db_slab) {
+__global__ __launch_bounds__(256) void SGC_XENT_KERNEL(xent_dw)(
+    SGC_XENT_STOP_PARAM const float *__restrict__ X, int64_t ldx, const float *__restrict__ G,
+    int ldg, int M, int K, int C, int rows_per, float *__restrict__ slab,
+    float *__restrict__ db_slab) {
+    SGC_XENT_STOP_TEST
     using VT = typename Vec<V>::T;
     const int lane = threadIdx.x & 63;
     const int w = threadIdx.x >> 6;
@@ -288,6 +318,8 @@ __global__ __launch_bounds__(256) void xent_dw_kernel(const float *__restrict__ 
             }
     }
 }
+#endif  // pass 2
+#ifndef SGC_XENT_STOP_PASS
 
 // ---- B': dW partial slabs on split-bf16 products (round 6) -----------------
 // The same slab decomposition as xent_dw_kernel, with the fp32 MFMA
@@ -533,12 +565,16 @@ __device__ __forceinline__ void buffer_load_floats(__amdgpu_buffer_rsrc_t r, uin
 constexpr int kDwColRanges = SGC_DW_COL_RANGES;  // row ranges (a multiple of 8: the XCD numbering)
 constexpr int kDwColWidth = 64;   // columns per block
 
+#endif  // !SGC_XENT_STOP_PASS
+#if !defined(SGC_XENT_STOP_PASS) || SGC_XENT_STOP_PASS == 2
 template <int NT>
-__global__ __launch_bounds__(256) void xent_dw_cols_kernel(
-    const float *__restrict__ X, int64_t ldx, const float *__restrict__ G, int ldg, int M, int K,
-    int C, int n_cblk, int R, float *__restrict__ slab, float *__restrict__ db_slab) {
+__global__ __launch_bounds__(256) void SGC_XENT_KERNEL(xent_dw_cols)(
+    SGC_XENT_STOP_PARAM const float *__restrict__ X, int64_t ldx, const float *__restrict__ G,
+    int ldg, int M, int K, int C, int n_cblk, int R, float *__restrict__ slab,
+    float *__restrict__ db_slab) {
     __shared__ f32x4 red[4][NT][4][64];  // [wave][class tile][q][lane] -> N-tiles e = 0..3
     __shared__ float dbr[4][NT * 16];
+    SGC_XENT_STOP_TEST
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform loop bounds
     const int i = lane & 15, g = lane >> 4;
@@ -700,15 +736,20 @@ __global__ __launch_bounds__(256) void xent_dw_cols_kernel(
         db_slab[(int64_t)r * (NT * 16) + threadIdx.x] =
             ((dbr[0][threadIdx.x] + dbr[1][threadIdx.x]) + dbr[2][threadIdx.x]) + dbr[3][threadIdx.x];
 }
+#endif  // pass 2
+#ifndef SGC_XENT_STOP_PASS
 
 // ---- C: fixed-order reductions ----------------------------------------------
 // dW: a block owns 64 consecutive elements; wave w sums slabs [w*n/4, (w+1)*n/4)
 // in order (coalesced 256-B rows of each slab), then wave 0 adds the four
 // partials in order.  Deterministic; ~n/4 loads in flight per lane.
-__global__ __launch_bounds__(256) void xent_reduce_dw_kernel(const float *__restrict__ slab,
-                                                             int n_slabs, int C, int K, int C16,
-                                                             float *__restrict__ dW) {
+#endif  // !SGC_XENT_STOP_PASS
+#if !defined(SGC_XENT_STOP_PASS) || SGC_XENT_STOP_PASS == 2
+__global__ __launch_bounds__(256) void SGC_XENT_KERNEL(xent_reduce_dw)(
+    SGC_XENT_STOP_PARAM const float *__restrict__ slab, int n_slabs, int C, int K, int C16,
+    float *__restrict__ dW) {
     __shared__ float part[4][64];
+    SGC_XENT_STOP_TEST
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t e = blockIdx.x * 64LL + lane;
     const int64_t total = (int64_t)C * K;
@@ -732,6 +773,8 @@ __global__ __launch_bounds__(256) void xent_reduce_dw_kernel(const float *__rest
     __syncthreads();
     if (w == 0 && e < total) dW[e] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
 }
+#endif  // pass 2
+#ifndef SGC_XENT_STOP_PASS
 
 // dW as xent_reduce_dw_kernel, and in the same launch db: blocks past dW's
 // (one per 64 classes) sum db_slab's column over the slabs, wave w a quarter
@@ -792,10 +835,13 @@ __global__ __launch_bounds__(256) void xent_reduce_dw_db_kernel(
 
 // loss (double, block C) and db (block c < C): 256 threads per block, strided
 // partial sums then a fixed-shape LDS tree -- deterministic.
-__global__ __launch_bounds__(256) void xent_reduce_small_kernel(
-    const double *__restrict__ loss_part, const float *__restrict__ db_part, int n_waves, int C,
-    int ldg, double inv_m, float *__restrict__ loss, float *__restrict__ db) {
+#endif  // !SGC_XENT_STOP_PASS
+#if !defined(SGC_XENT_STOP_PASS) || SGC_XENT_STOP_PASS == 2
+__global__ __launch_bounds__(256) void SGC_XENT_KERNEL(xent_reduce_small)(
+    SGC_XENT_STOP_PARAM const double *__restrict__ loss_part, const float *__restrict__ db_part,
+    int n_waves, int C, int ldg, double inv_m, float *__restrict__ loss, float *__restrict__ db) {
     __shared__ double red[256];
+    SGC_XENT_STOP_TEST
     const int t = threadIdx.x, c = blockIdx.x;
     if (c < C && !db) return;
     double s = 0.0;
@@ -819,6 +865,19 @@ __global__ __launch_bounds__(256) void xent_reduce_small_kernel(
             db[c] = (float)red[0];
     }
 }
+#endif  // pass 2
+#ifndef SGC_XENT_STOP_PASS
+// The second pass: the kernels of B and C above once more, as <name>_stop_kernel.
+#undef SGC_XENT_KERNEL
+#undef SGC_XENT_STOP_PARAM
+#undef SGC_XENT_STOP_TEST
+#define SGC_XENT_KERNEL(name) name##_stop_kernel
+#define SGC_XENT_STOP_PARAM const int64_t *__restrict__ stop,
+#define SGC_XENT_STOP_TEST \
+    if (*stop != 0) return;
+#define SGC_XENT_STOP_PASS 2
+#include "xent.hip"
+#undef SGC_XENT_STOP_PASS
 
 // The two reductions above in one launch, with the Adam update
 // (adam_update.h) applied by the thread that holds the finished gradient
@@ -897,12 +956,17 @@ __global__ __launch_bounds__(256) void xent_reduce_adam_kernel(
     }
 }
 
+// (stop, here and below: null for the plain kernels, else the device word the
+// stop-aware kernels test -- same grid, same arguments)
 template <int V, int NT>
-hipError_t launch_fwd(const float *X, int64_t ldx, const float *W, const float *b,
-                      const int64_t *labels, int M, int K, int C, float *G, int ldg,
+hipError_t launch_fwd(const int64_t *stop, const float *X, int64_t ldx, const float *W,
+                      const float *b, const int64_t *labels, int M, int K, int C, float *G, int ldg,
                       double *loss_part, float *db_part, float *logits, int64_t ldl,
                       hipStream_t s) {
     const int blocks = (M + kLdsBM - 1) / kLdsBM;
+    if (stop)
+        return launch_xent_fwd_stop(V, NT, stop, X, ldx, W, b, labels, M, K, C, G, ldg, loss_part,
+                                    db_part, logits, ldl, s);
     if (g_tile_buffers == 1)
         hipLaunchKernelGGL((xent_fwd_kernel<V, NT, 1>), dim3(blocks), dim3(256), 0, s, X, ldx, W,
                            b, labels, M, K, C, 1.0f / (float)M, G, ldg, loss_part, db_part, logits,
@@ -915,11 +979,16 @@ hipError_t launch_fwd(const float *X, int64_t ldx, const float *W, const float *
 }
 
 template <int V, int NT>
-hipError_t launch_dw(const float *X, int64_t ldx, const float *G, int ldg, int M, int K, int C,
-                     int n_slabs, int rows_per, float *slab, float *db_slab, hipStream_t s) {
+hipError_t launch_dw(const int64_t *stop, const float *X, int64_t ldx, const float *G, int ldg,
+                     int M, int K, int C, int n_slabs, int rows_per, float *slab, float *db_slab,
+                     hipStream_t s) {
     constexpr int CT = (NT >= 3) ? 2 : 4;
-    hipLaunchKernelGGL((xent_dw_kernel<V, NT, CT>), dim3(n_slabs), dim3(256), 0, s, X, ldx, G,
-                       ldg, M, K, C, rows_per, slab, db_slab);
+    if (stop)
+        hipLaunchKernelGGL((xent_dw_stop_kernel<V, NT, CT>), dim3(n_slabs), dim3(256), 0, s, stop,
+                           X, ldx, G, ldg, M, K, C, rows_per, slab, db_slab);
+    else
+        hipLaunchKernelGGL((xent_dw_kernel<V, NT, CT>), dim3(n_slabs), dim3(256), 0, s, X, ldx, G,
+                           ldg, M, K, C, rows_per, slab, db_slab);
     return hipGetLastError();
 }
 
@@ -939,13 +1008,17 @@ inline int dw_col_ranges(int64_t M) {
 }
 
 template <int NT>
-hipError_t launch_dw_cols(const float *X, int64_t ldx, const float *G, int ldg, int M, int K,
-                          int C, float *slab, float *db_slab, hipStream_t s) {
+hipError_t launch_dw_cols(const int64_t *stop, const float *X, int64_t ldx, const float *G, int ldg,
+                          int M, int K, int C, float *slab, float *db_slab, hipStream_t s) {
     const int R = dw_col_ranges(M);
     const int n_cblk = (K + kDwColWidth - 1) / kDwColWidth;
     const int blocks = n_cblk * ((R + 7) / 8) * 8;
-    hipLaunchKernelGGL((xent_dw_cols_kernel<NT>), dim3(blocks), dim3(256), 0, s, X, ldx, G, ldg, M,
-                       K, C, n_cblk, R, slab, db_slab);
+    if (stop)
+        hipLaunchKernelGGL((xent_dw_cols_stop_kernel<NT>), dim3(blocks), dim3(256), 0, s, stop, X,
+                           ldx, G, ldg, M, K, C, n_cblk, R, slab, db_slab);
+    else
+        hipLaunchKernelGGL((xent_dw_cols_kernel<NT>), dim3(blocks), dim3(256), 0, s, X, ldx, G, ldg,
+                           M, K, C, n_cblk, R, slab, db_slab);
     return hipGetLastError();
 }
 
@@ -996,9 +1069,64 @@ struct XentPartials {
     float *slab;
     int C16, waves, n_parts;
 };
-static int xent_launch_ab(const float *X, int64_t ldx, const float *W, const float *b,
-                          const int64_t *labels, int64_t M, int64_t K, int64_t C, float *logits,
-                          int64_t ldl, void *ws, hipStream_t s, XentPartials &out);
+static int xent_launch_ab(const int64_t *stop, const float *X, int64_t ldx, const float *W,
+                          const float *b, const int64_t *labels, int64_t M, int64_t K, int64_t C,
+                          float *logits, int64_t ldl, void *ws, hipStream_t s, XentPartials &out);
+
+// The four launches of the fused step (arguments checked by the caller): A and
+// B, then the two reductions.  stop: null, or the device word behind which
+// every one of the four runs (the stop-aware kernels).
+static int xent_step_launches(const int64_t *stop, const float *X, int64_t ldx, const float *W,
+                              const float *b, const int64_t *labels, int64_t M, int64_t K,
+                              int64_t C, float *loss, float *dW, float *db, float *logits,
+                              int64_t ldl, void *ws, hipStream_t s) {
+    XentPartials part;
+    if (const int rc = xent_launch_ab(stop, X, ldx, W, b, labels, M, K, C, logits, ldl, ws, s, part))
+        return rc;
+    const int64_t ck = C * K;
+    const dim3 dw_grid((unsigned)((ck + 63) / 64)), small_grid((unsigned)C + 1);
+    if (stop)
+        hipLaunchKernelGGL(xent_reduce_dw_stop_kernel, dw_grid, dim3(256), 0, s, stop, part.slab,
+                           part.n_parts, (int)C, (int)K, part.C16, dW);
+    else
+        hipLaunchKernelGGL(xent_reduce_dw_kernel, dw_grid, dim3(256), 0, s, part.slab,
+                           part.n_parts, (int)C, (int)K, part.C16, dW);
+    SGC_HIP_CHECK(hipGetLastError());
+    if (stop)
+        hipLaunchKernelGGL(xent_reduce_small_stop_kernel, small_grid, dim3(256), 0, s, stop,
+                           part.loss_part, part.db_part, part.waves, (int)C, part.C16,
+                           1.0 / (double)M, loss, db);
+    else
+        hipLaunchKernelGGL(xent_reduce_small_kernel, small_grid, dim3(256), 0, s, part.loss_part,
+                           part.db_part, part.waves, (int)C, part.C16, 1.0 / (double)M, loss, db);
+    SGC_HIP_CHECK(hipGetLastError());
+    return SGC_OK;
+}
+
+// ---- the closure of sgc_train_lbfgs_f32 (lbfgs.hip) ----------------------------
+// sgc_linear_xent_f32's launches behind the L-BFGS state's stop word: the same
+// kernel selection, grids, workspace layout and arithmetic, so loss, dW and db
+// carry sgc_linear_xent_f32's bits while the step runs and stay untouched once
+// it has stopped.  xent_closure_check: the limits of those launches, for the
+// caller to test before its first device call.
+int xent_closure_check(const char *what, int64_t M, int64_t K, int64_t C, int64_t ldx) {
+    SGC_REQUIRE(M < INT32_MAX && K < INT32_MAX, SGC_ERANGE, "%s: too large", what);
+    SGC_REQUIRE(block_tile_fits(ldx, K, C), SGC_ERANGE,
+                "%s: ldx=%lld / K=%lld past the tile's 31-bit offsets", what, (long long)ldx,
+                (long long)K);
+    const int64_t n_slabs = std::min<int64_t>(kDwSlabs, (M + 255) / 256);
+    const int64_t rows_per = ((M + n_slabs - 1) / n_slabs + 3) / 4 * 4;
+    SGC_REQUIRE(dw_slab_fits(rows_per, ldx, (C + 15) / 16 * 16), SGC_ERANGE,
+                "%s: %lld rows x ldx %lld past the dW kernel's 31-bit offsets", what,
+                (long long)rows_per, (long long)ldx);
+    return SGC_OK;
+}
+
+int xent_closure(const int64_t *stop, const float *X, int64_t ldx, const float *W, const float *b,
+                 const int64_t *labels, int64_t M, int64_t K, int64_t C, float *loss, float *dW,
+                 float *db, void *ws, hipStream_t s) {
+    return xent_step_launches(stop, X, ldx, W, b, labels, M, K, C, loss, dW, db, nullptr, 0, ws, s);
+}
 
 int linear_xent_f32(const float *X, int64_t ldx, const float *W, const float *b,
                     const int64_t *labels, int64_t M, int64_t K, int64_t C, float *loss,
@@ -1016,25 +1144,15 @@ int linear_xent_f32(const float *X, int64_t ldx, const float *W, const float *b,
     const int64_t need = xent_workspace_bytes(M, K, C);
     SGC_REQUIRE(ws_bytes >= need, SGC_ENOMEM, "linear_xent: workspace %lld < %lld",
                 (long long)ws_bytes, (long long)need);
-    XentPartials part;
-    if (const int rc = xent_launch_ab(X, ldx, W, b, labels, M, K, C, logits, ldl, ws, s, part))
-        return rc;
-    const int64_t ck = C * K;
-    hipLaunchKernelGGL(xent_reduce_dw_kernel, dim3((unsigned)((ck + 63) / 64)), dim3(256), 0, s,
-                       part.slab, part.n_parts, (int)C, (int)K, part.C16, dW);
-    SGC_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(xent_reduce_small_kernel, dim3((unsigned)C + 1), dim3(256), 0, s,
-                       part.loss_part, part.db_part, part.waves, (int)C, part.C16, 1.0 / (double)M,
-                       loss, db);
-    SGC_HIP_CHECK(hipGetLastError());
-    return SGC_OK;
+    return xent_step_launches(nullptr, X, ldx, W, b, labels, M, K, C, loss, dW, db, logits, ldl, ws,
+                              s);
 }
 
 // Launches A and B of the fused step (the caller has checked the shape and the
 // workspace size); `out` says where they left G and the partials.
-static int xent_launch_ab(const float *X, int64_t ldx, const float *W, const float *b,
-                          const int64_t *labels, int64_t M, int64_t K, int64_t C, float *logits,
-                          int64_t ldl, void *ws, hipStream_t s, XentPartials &out) {
+static int xent_launch_ab(const int64_t *stop, const float *X, int64_t ldx, const float *W,
+                          const float *b, const int64_t *labels, int64_t M, int64_t K, int64_t C,
+                          float *logits, int64_t ldl, void *ws, hipStream_t s, XentPartials &out) {
     const int NT = (int)((C + 15) / 16);
     const int C16 = NT * 16;
     const int waves = (int)((M + kLdsBM - 1) / kLdsBM * 4);
@@ -1065,30 +1183,30 @@ static int xent_launch_ab(const float *X, int64_t ldx, const float *W, const flo
     hipError_t e = hipSuccess;
 #define SGC_XENT_DISPATCH(VV)                                                                    \
     switch (NT) {                                                                                \
-        case 1: e = launch_fwd<VV, 1>(X, ldx, W, b, labels, (int)M, (int)K, (int)C, G, C16,      \
+        case 1: e = launch_fwd<VV, 1>(stop, X, ldx, W, b, labels, (int)M, (int)K, (int)C, G, C16,      \
                                       loss_part, db_part, logits, ldl, s);                       \
             if (e == hipSuccess)                                                                 \
-                e = cols ? launch_dw_cols<1>(X, ldx, G, C16, (int)M, (int)K, (int)C, slab, nullptr, s) \
-                         : launch_dw<VV, 1>(X, ldx, G, C16, (int)M, (int)K, C16, n_slabs, rows_per,   \
+                e = cols ? launch_dw_cols<1>(stop, X, ldx, G, C16, (int)M, (int)K, (int)C, slab, nullptr, s) \
+                         : launch_dw<VV, 1>(stop, X, ldx, G, C16, (int)M, (int)K, C16, n_slabs, rows_per,   \
                                               slab, nullptr, s);                                        \
             break;                                                                               \
-        case 2: e = launch_fwd<VV, 2>(X, ldx, W, b, labels, (int)M, (int)K, (int)C, G, C16,      \
+        case 2: e = launch_fwd<VV, 2>(stop, X, ldx, W, b, labels, (int)M, (int)K, (int)C, G, C16,      \
                                       loss_part, db_part, logits, ldl, s);                       \
             if (e == hipSuccess)                                                                 \
-                e = cols ? launch_dw_cols<2>(X, ldx, G, C16, (int)M, (int)K, (int)C, slab, nullptr, s) \
-                         : launch_dw<VV, 2>(X, ldx, G, C16, (int)M, (int)K, C16, n_slabs, rows_per,   \
+                e = cols ? launch_dw_cols<2>(stop, X, ldx, G, C16, (int)M, (int)K, (int)C, slab, nullptr, s) \
+                         : launch_dw<VV, 2>(stop, X, ldx, G, C16, (int)M, (int)K, C16, n_slabs, rows_per,   \
                                               slab, nullptr, s);                                        \
             break;                                                                               \
-        case 3: e = launch_fwd<VV, 3>(X, ldx, W, b, labels, (int)M, (int)K, (int)C, G, C16,      \
+        case 3: e = launch_fwd<VV, 3>(stop, X, ldx, W, b, labels, (int)M, (int)K, (int)C, G, C16,      \
                                       loss_part, db_part, logits, ldl, s);                       \
             if (e == hipSuccess)                                                                 \
-                e = cols ? launch_dw_cols<3>(X, ldx, G, C16, (int)M, (int)K, (int)C, slab, nullptr, s) \
-                         : launch_dw<VV, 3>(X, ldx, G, C16, (int)M, (int)K, C16, n_slabs, rows_per,   \
+                e = cols ? launch_dw_cols<3>(stop, X, ldx, G, C16, (int)M, (int)K, (int)C, slab, nullptr, s) \
+                         : launch_dw<VV, 3>(stop, X, ldx, G, C16, (int)M, (int)K, C16, n_slabs, rows_per,   \
                                               slab, nullptr, s);                                        \
             break;                                                                               \
-        default: e = launch_fwd<VV, 4>(X, ldx, W, b, labels, (int)M, (int)K, (int)C, G, C16,     \
+        default: e = launch_fwd<VV, 4>(stop, X, ldx, W, b, labels, (int)M, (int)K, (int)C, G, C16,     \
                                        loss_part, db_part, logits, ldl, s);                      \
-            if (e == hipSuccess) e = launch_dw<VV, 4>(X, ldx, G, C16, (int)M, (int)K, C16,    \
+            if (e == hipSuccess) e = launch_dw<VV, 4>(stop, X, ldx, G, C16, (int)M, (int)K, C16,    \
                                                       n_slabs, rows_per, slab, nullptr, s);                        \
             break;                                                                               \
     }
@@ -1125,7 +1243,7 @@ int xent_adam_epoch(const float *X, int64_t ldx, float *W, float *b, const int64
     SGC_REQUIRE(ws_bytes >= need, SGC_ENOMEM, "train_adam: workspace %lld < %lld",
                 (long long)ws_bytes, (long long)need);
     XentPartials part;
-    if (const int rc = xent_launch_ab(X, ldx, W, b, labels, M, K, C, nullptr, 0, ws, s, part))
+    if (const int rc = xent_launch_ab(nullptr, X, ldx, W, b, labels, M, K, C, nullptr, 0, ws, s, part))
         return rc;
     const int dw_blocks = (int)((C * K + 63) / 64);
     hipLaunchKernelGGL(xent_reduce_adam_kernel, dim3((unsigned)(dw_blocks + C + 1)), dim3(256), 0,
@@ -1202,11 +1320,11 @@ int linear_backward_f32(const float *X, int64_t ldx, const float *dY, int64_t ld
                     (long long)ldx);
         n_parts = dw_col_ranges(M);
         switch (NT) {
-            case 1: e = launch_dw_cols<1>(X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, slab,
+            case 1: e = launch_dw_cols<1>(nullptr, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, slab,
                                           db_slab, s); break;
-            case 2: e = launch_dw_cols<2>(X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, slab,
+            case 2: e = launch_dw_cols<2>(nullptr, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, slab,
                                           db_slab, s); break;
-            default: e = launch_dw_cols<3>(X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, slab,
+            default: e = launch_dw_cols<3>(nullptr, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, slab,
                                            db_slab, s); break;
         }
     } else if (split) {
@@ -1223,13 +1341,13 @@ int linear_backward_f32(const float *X, int64_t ldx, const float *dY, int64_t ld
     } else {
 #define SGC_BWD_DISPATCH(VV)                                                                     \
     switch (NT) {                                                                                \
-        case 1: e = launch_dw<VV, 1>(X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,      \
+        case 1: e = launch_dw<VV, 1>(nullptr, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,      \
                                      rows_per, slab, db_slab, s); break;                         \
-        case 2: e = launch_dw<VV, 2>(X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,      \
+        case 2: e = launch_dw<VV, 2>(nullptr, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,      \
                                      rows_per, slab, db_slab, s); break;                         \
-        case 3: e = launch_dw<VV, 3>(X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,      \
+        case 3: e = launch_dw<VV, 3>(nullptr, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,      \
                                      rows_per, slab, db_slab, s); break;                         \
-        default: e = launch_dw<VV, 4>(X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,     \
+        default: e = launch_dw<VV, 4>(nullptr, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,     \
                                       rows_per, slab, db_slab, s); break;                        \
     }
         if (V == 4) {
@@ -1266,3 +1384,4 @@ const char *linear_backward_kernel_name(int64_t M, int64_t K, int64_t ldx, int64
 SGC_WARM_UNIT(warm_xent)
 
 }  // namespace sgc
+#endif  // !SGC_XENT_STOP_PASS

@@ -19,6 +19,21 @@ elements in all, history_size <= 1024 and line_search_fn is None.  Anything
 else -- CPU tensors (the reference's --no-cuda mode), strong-Wolfe, larger
 models -- is torch.optim.LBFGS.step itself, bit for bit.
 
+LBFGS.run_steps(model, features, labels, steps) is `steps` such steps with the
+reference closure (zero_grad, F.cross_entropy(model(features), labels),
+backward).  It is one host call (sgc_train_lbfgs_f32: the closures too are
+launches behind the device stop word, so a stopped step costs empty launches
+only) and one read-back of the per-step status table when: the device path
+above holds; the model is exactly sgc_amd.models.SGC with a bias and the
+optimiser's parameters are [W.weight, W.bias] in that order; the features are
+float32 on the parameters' ROCm device, 2-D with K columns (copied only where
+the layout needs it); the labels are int64 on that device, one per row, none
+of them -100; and there are at most 64 classes.  Anything else -- CPU tensors,
+bfloat16 / float16 features, rows labelled -100, strong-Wolfe, more than 64
+classes, a foreign model, another parameter order -- is the literal loop of
+step() calls.  The fused run is bit-identical to the stepwise device path
+driven with the closure `sgc_cross_entropy(model, x, y).backward()`.
+
 Results of the device path are tolerance-equal to torch's (fp64-accumulated
 dot products in a fixed order; torch sums in fp32) and bitwise reproducible
 run to run.  state_dict() does not carry the device state.
@@ -54,6 +69,12 @@ def _read_status(lib, state, stream):
     return tuple(out)
 
 
+def _read_status_trace(table):
+    """run_steps' status table as one tuple per step: the one read-back (and
+    host synchronisation) of a fused run."""
+    return [tuple(row) for row in table.cpu().view(-1, 6).tolist()]
+
+
 class LBFGS(torch.optim.LBFGS):
     def __init__(self, params, lr=1, max_iter=20, max_eval=None, tolerance_grad=1e-7,
                  tolerance_change=1e-9, history_size=100, line_search_fn=None, poll_every=None):
@@ -66,6 +87,7 @@ class LBFGS(torch.optim.LBFGS):
         self._dev_state = None  # uint8 device tensor (sgc_lbfgs_workspace bytes)
         self._dev_key = None    # (parameter identities and shapes, history_size) it was built for
         self.last_status = None  # (n_iter, func_evals, iters, evals, stop, hist_len) of the last step
+        self.step_statuses = []  # the same per step of the last run_steps()
 
     def device_path(self):
         """Whether step() runs on the device (see the module docstring)."""
@@ -98,19 +120,10 @@ class LBFGS(torch.optim.LBFGS):
         group = self.param_groups[0]
         ps = self._params
         dev = ps[0].device
-        n = sum(p.numel() for p in ps)
         closure = torch.enable_grad()(closure)
         with torch.cuda.device(dev):
             stream = _lib.stream_handle(dev)
-            if self._dev_state is None:
-                nbytes = lib.sgc_lbfgs_workspace(n, group["history_size"])
-                if nbytes <= 0:
-                    _lib.check(1, "lbfgs_workspace")
-                state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                _lib.check(lib.sgc_lbfgs_init(_lib.ptr(state), nbytes, n, group["history_size"],
-                                              stream), "lbfgs_init")
-                self._dev_state, self._dev_key = state, self._key()
-            state = self._dev_state
+            state = self._ensure_state(lib, dev, stream)
             nt = len(ps)
             p_ptrs = (ctypes.c_void_p * nt)(*[p.data_ptr() for p in ps])
             numels = (ctypes.c_int64 * nt)(*[p.numel() for p in ps])
@@ -142,6 +155,112 @@ class LBFGS(torch.optim.LBFGS):
         st = self.state[ps[0]]
         st["n_iter"], st["func_evals"] = int(status[0]), int(status[1])
         return orig_loss
+
+    def _ensure_state(self, lib, dev, stream):
+        """The device state, built (and zeroed) on first use."""
+        if self._dev_state is None:
+            group = self.param_groups[0]
+            n = sum(p.numel() for p in self._params)
+            nbytes = lib.sgc_lbfgs_workspace(n, group["history_size"])
+            if nbytes <= 0:
+                _lib.check(1, "lbfgs_workspace")
+            state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.sgc_lbfgs_init(_lib.ptr(state), nbytes, n, group["history_size"],
+                                          stream), "lbfgs_init")
+            self._dev_state, self._dev_key = state, self._key()
+        return self._dev_state
+
+    # -- whole steps in one host call ---------------------------------------------------
+    def _fused_plan(self, model, features, labels):
+        """(W, b) when run_steps can run as one sgc_train_lbfgs_f32 call."""
+        from .models import SGC
+        if type(model) is not SGC or model.W.bias is None or not self.device_path():
+            return None
+        W, b = model.W.weight, model.W.bias
+        ps = self._params
+        if len(ps) != 2 or ps[0] is not W or ps[1] is not b:
+            return None
+        x, y = features, labels
+        if not (isinstance(x, torch.Tensor) and x.device == W.device and
+                x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 1 and
+                x.shape[1] == W.shape[1] and 1 <= W.shape[0] <= 64):
+            return None
+        if not (isinstance(y, torch.Tensor) and y.dtype == torch.int64 and y.device == x.device and
+                y.shape == (x.shape[0],)):
+            return None
+        if not (W.requires_grad and b.requires_grad):
+            return None
+        if _labels_have_ignored(y, W.shape[0]):
+            return None
+        return W, b
+
+    def run_steps(self, model, features, labels, steps):
+        """`steps` times self.step(closure) with the reference closure --
+        zero_grad, F.cross_entropy(model(features), labels), backward
+        (reddit.py:51-64).  Returns the [steps] tensor of each step's first
+        closure loss (what step() returns), None when steps == 0 (nothing is
+        touched).  Afterwards `step_statuses` holds one status tuple per step
+        (None for a step torch's own step() ran) and `last_status` the last.
+
+        The fused path (module docstring) is one sgc_train_lbfgs_f32 call and
+        one read-back of the status table, the call's only synchronisation
+        after the labels' one range check; the parameters' .grad is left None.
+        Everything else runs the literal loop.  A label outside [0, C) other
+        than -100 raises IndexError on either path."""
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError(f"steps must be >= 0, got {steps}")
+        if steps == 0:
+            return None
+        plan = self._fused_plan(model, features, labels)
+        model.train()
+        if plan is None:
+            def closure():
+                self.zero_grad()
+                loss = F.cross_entropy(model(features), labels)
+                loss.backward()
+                return loss
+            losses, self.step_statuses = [], []
+            for _ in range(steps):
+                self.last_status = None
+                loss = self.step(closure)
+                losses.append(torch.as_tensor(loss).detach())
+                self.step_statuses.append(self.last_status)
+            return torch.stack(losses)
+        if self._dev_state is not None and self._key() != self._dev_key:
+            raise ValueError("sgc_amd.optim.LBFGS: the parameter list or history_size changed "
+                             "after the first step")
+        W, b = plan
+        self.zero_grad(set_to_none=True)
+        group = self.param_groups[0]
+        x = features.detach()
+        if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+            x = x.contiguous()
+        y = labels.contiguous()
+        M, K = x.shape
+        C = W.shape[0]
+        dev = x.device
+        lib = _lib.load()
+        ws_bytes = lib.sgc_train_lbfgs_workspace(M, K, C)
+        ws = getattr(self, "_train_ws", None)
+        if ws is None or ws.numel() < ws_bytes or ws.device != dev:
+            ws = self._train_ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=dev)
+        losses = torch.empty(steps, dtype=torch.float32, device=dev)
+        table = torch.empty(steps * 6, dtype=torch.int64, device=dev)
+        with torch.no_grad(), torch.cuda.device(dev):
+            stream = _lib.stream_handle(dev)
+            state = self._ensure_state(lib, dev, stream)
+            _lib.check(lib.sgc_train_lbfgs_f32(
+                _lib.ptr(x), x.stride(0), _lib.ptr(W), _lib.ptr(b), _lib.ptr(y), M, K, C,
+                _lib.ptr(state), steps, float(group["lr"]), group["max_iter"], group["max_eval"],
+                float(group["tolerance_grad"]), float(group["tolerance_change"]),
+                _lib.ptr(losses), _lib.ptr(table), _lib.ptr(ws), ws.numel(), stream),
+                "train_lbfgs_f32")
+            self.step_statuses = _read_status_trace(table)
+        self.last_status = self.step_statuses[-1]
+        st = self.state[self._params[0]]
+        st["n_iter"], st["func_evals"] = int(self.last_status[0]), int(self.last_status[1])
+        return losses
 
     @staticmethod
     def _device_loss(loss, dev):
