@@ -363,6 +363,24 @@ int sgc_spmm_csr_f32_ex3(const int32_t *row_ptr, const int32_t *col_idx, const f
                          int32_t heavy_threshold, uint32_t flags, int64_t n_nonempty,
                          int64_t n_not_wide, int32_t wide_max_nnz, void *stream);
 
+/* Which kernels an sgc_spmm_csr_f32_ex3 launch of these arguments would run
+ * under the knobs in force (measurement and tests; the counterpart of
+ * sgc_linear_kernel_name).  Host only: it needs no device, X and Y are used
+ * for their alignment and never dereferenced, plan for being NULL or not.
+ * Returns a thread-local string, valid until the thread's next call:
+ *   "spmm_rows_kernel<LB=..,VH=..,UH=16,O32=..,QV=..,HF=..,WD=..> LR=.. slices=..
+ *    n_sub=.. bits=<heavy_pairs / pipe2 bits passed> grid=XxY wide=<wide items>
+ *    hub=<none|concurrent|serial|fused>[ spmm_hub_kernel<HC,NL> grid=..]"
+ * or "spmm_csr_kernel<V=..,C=..,UH=16,HF=..> LR=0 slices=.. n_sub=.. bits=.. grid=XxY
+ *    wide=0 hub=..";
+ * "none" for a launch that runs no light kernel (no rows, SGC_SPMM_HUB_ONLY)
+ * and for arguments sgc_spmm_csr_f32_ex3 would reject (sgc_last_error says why). */
+const char *sgc_spmm_kernel_name(int64_t row_begin, int64_t row_end, const float *X, int64_t ldx,
+                                 const float *Y, int64_t ldy, int64_t F, const int32_t *plan,
+                                 int64_t n_heavy, int64_t n_hub, int32_t heavy_threshold,
+                                 uint32_t flags, int64_t n_nonempty, int64_t n_not_wide,
+                                 int32_t wide_max_nnz);
+
 /* K hops X_K = S^K X_0 over all n_rows rows (utils.py:92-97, the whole
  * sgc_precompute loop).  out (row stride ldo) receives X_K.  Intermediate
  * hops live in the workspace with 128-B aligned rows (ld = F rounded up to 32

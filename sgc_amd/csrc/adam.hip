@@ -40,10 +40,10 @@
 #include <cmath>
 
 #include "adam_update.h"
+#include "internal.h"
 
 namespace sgc {
 
-hipError_t persistent_setup(const void *kernel, int *cus);  // linear.hip
 
 // sgc_set_tuning("adam_kernel"): 0 auto, 1 general, 2 small (where eligible).
 int g_adam_kernel = 0;
@@ -391,7 +391,6 @@ int adam_step(int32_t n_tensors, float *const *params, const float *const *grads
     return SGC_OK;
 }
 
-int64_t xent_workspace_bytes(int64_t M, int64_t K, int64_t C);  // xent.hip
 
 int64_t train_adam_workspace(int64_t M, int64_t K, int64_t C) {
     if (M <= 0 || K <= 0 || C <= 0 || C > 64) return 0;

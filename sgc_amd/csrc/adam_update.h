@@ -34,13 +34,6 @@ __device__ __forceinline__ void adam_update(float &p, float &m, float &v, float 
 AdamCoef adam_coef(int64_t step, double lr, double beta1, double beta2, double eps,
                    double weight_decay);
 
-// xent.hip: one epoch of the general schedule (launches A and B of the fused
-// classifier step, then the reduce + Adam kernel).  Arguments as
-// sgc_train_adam_f32; ws as linear_xent_f32's.
-int xent_adam_epoch(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels,
-                    int64_t M, int64_t K, int64_t C, float *mW, float *vW, float *mb, float *vb,
-                    const AdamCoef &coef, float *loss_out, void *ws, int64_t ws_bytes,
-                    hipStream_t s);
-int xent_adam_check(int64_t M, int64_t K, int64_t C, int64_t ldx);
+// (xent.hip's xent_adam_epoch / xent_adam_check: internal.h)
 
 }  // namespace sgc

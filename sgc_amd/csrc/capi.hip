@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "internal.h"
 
 namespace sgc {
 
@@ -18,161 +19,6 @@ void set_error(const char *fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-
-int coo_to_csr_workspace(int64_t n_rows, int64_t nnz, size_t *bytes);
-int coo_to_csr(const int64_t *rows, const int64_t *cols, const float *vals, int64_t nnz,
-               int64_t n_rows, int64_t n_cols, int32_t *row_ptr, int32_t *col_idx,
-               float *val_out, void *ws, size_t ws_bytes, uint32_t *status_host,
-               hipStream_t stream);
-int csr64_to_csr(const int64_t *crow, const int64_t *col, const float *vals, int64_t nnz,
-                 int64_t n_rows, int64_t n_cols, int32_t *row_ptr, int32_t *col_idx,
-                 float *val_out, uint32_t *status_host, hipStream_t stream);
-int build_plan(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
-               int32_t hub_threshold, int32_t *plan, int64_t capacity, int64_t *n_heavy_host,
-               int64_t *n_hub_host, hipStream_t stream);
-int light_order(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
-                int32_t *light, int64_t *n_light_host, hipStream_t stream);
-int launch_spmm(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
-                int64_t row_begin, int64_t row_end, const float *X, int64_t ldx, float *Y,
-                int64_t ldy, int64_t F, const int32_t *heavy_rows, int64_t n_heavy,
-                int64_t n_hub, int32_t heavy_threshold, uint32_t flags, hipStream_t stream,
-                int64_t n_nonempty = -1, int64_t n_not_wide = -1, int32_t wide_max_nnz = 0);
-int launch_spmm_x16(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
-                    int64_t row_begin, int64_t row_end, const void *X, int32_t x_dtype,
-                    int64_t ldx, void *Y, int32_t y_dtype, int64_t ldy, int64_t F,
-                    const int32_t *heavy_rows, int64_t n_heavy, int64_t n_hub,
-                    int32_t heavy_threshold, uint32_t flags, hipStream_t stream);
-int launch_pad_rows(const float *src, int64_t lds, float *dst, int64_t ldd, int64_t n_rows,
-                    int64_t F, hipStream_t stream);
-int launch_copy_blocks(const float *src, int64_t lds, float *dst, int64_t ldd, int32_t nseg,
-                       const int64_t *segs, hipStream_t stream);
-int launch_pull_blocks(int32_t nseg, const int64_t *segs, float *dst, int64_t ldd,
-                       hipStream_t stream);
-int launch_wait_flags(int32_t n, const int64_t *flags, int32_t value, int32_t *err,
-                      int64_t timeout_us, hipStream_t stream);
-int launch_signal_flag(int32_t *flag, int32_t value, hipStream_t stream);
-int ipc_get_handle(const void *ptr, void *handle);
-int ipc_open(const void *handle, void **base, void **ptr);
-int ipc_close(void *base);
-size_t augnorm_scan_temp_bytes(int64_t n);
-int augnorm_count(const int32_t *row_ptr, const int32_t *col, const double *val, int64_t n,
-                  int64_t nnz, int32_t *out_row_ptr, double *rowsum, void *ws, size_t ws_bytes,
-                  int64_t *out_nnz_host, uint32_t *status_host, hipStream_t s);
-int augnorm_fill(const int32_t *row_ptr, const int32_t *col, const double *val, int64_t n,
-                 const double *d, int32_t *out_row_ptr, int32_t *out_col, float *out_val,
-                 void *ws, size_t ws_bytes, int64_t *out_nnz_host, hipStream_t s);
-int csr_to_coo64(const int32_t *row_ptr, const int32_t *col, int64_t n, int64_t *rows64,
-                 int64_t *cols64, hipStream_t s);
-int64_t xent_workspace_bytes(int64_t M, int64_t K, int64_t C);
-int linear_xent_f32(const float *X, int64_t ldx, const float *W, const float *b,
-                    const int64_t *labels, int64_t M, int64_t K, int64_t C, float *loss,
-                    float *dW, float *db, float *logits, int64_t ldl, void *ws, int64_t ws_bytes,
-                    hipStream_t s);
-int64_t cross_entropy_workspace(int64_t M, int64_t C);
-int cross_entropy_fwd_f32(const float *Y, int64_t ldy, const int64_t *labels, int64_t M, int64_t C,
-                          int64_t ignore_index, float *loss, float *inv_count, float *lse, void *ws,
-                          int64_t ws_bytes, hipStream_t s);
-int cross_entropy_bwd_f32(const float *Y, int64_t ldy, const int64_t *labels, const float *lse,
-                          const float *inv_count, const float *grad, int64_t M, int64_t C,
-                          int64_t ignore_index, float *dY, int64_t lddy, hipStream_t s);
-int64_t linear_backward_workspace_bytes(int64_t M, int64_t K, int64_t C);
-int linear_backward_f32(const float *X, int64_t ldx, const float *dY, int64_t ldd, int64_t M,
-                        int64_t K, int64_t C, float *dW, float *db, void *ws, int64_t ws_bytes,
-                        hipStream_t s);
-int64_t subgraph_workspace(int64_t n, int64_t m, int64_t nnz);
-int subgraph_count(const int32_t *row_ptr, const int32_t *col, int64_t n, const int64_t *idx,
-                   int64_t m, int64_t nnz, int32_t *out_row_ptr, void *ws, int64_t ws_bytes,
-                   int64_t *out_nnz_host, uint32_t *status_host, hipStream_t s);
-int subgraph_fill(const int32_t *row_ptr, const int32_t *col, const double *val, int64_t n,
-                  const int64_t *idx, int64_t m, int64_t nnz, const int32_t *out_row_ptr,
-                  int32_t *out_col, double *out_val, void *ws, int64_t ws_bytes, hipStream_t s);
-int set_tuning(const char *key, int64_t value);
-int64_t get_tuning(const char *key);
-int timing_enable(int on);
-int timing_collect(float *light_ms, float *hub_ms, int64_t capacity, int64_t *n_host);
-int timing_collect_ex(float *light_ms, float *hub_ms, float *span_ms, int32_t *kernel,
-                      int64_t capacity, int64_t *n_host);
-int coo_to_csr_cpu(const int64_t *rows, const int64_t *cols, const float *vals, int64_t nnz,
-                   int64_t n_rows, int64_t n_cols, int32_t *row_ptr, int32_t *col_idx,
-                   float *val_out, uint32_t *status_host);
-int spmm_cpu(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t row_begin,
-             int64_t row_end, const float *X, int64_t ldx, float *Y, int64_t ldy, int64_t F,
-             int32_t n_threads, bool accum);
-int64_t propagate_cpu_workspace(int64_t n_rows, int64_t F, int32_t K);
-int propagate_cpu(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
-                  int64_t n_rows, const float *X0, int64_t ldx, float *out, int64_t ldo, int64_t F,
-                  int32_t K, void *workspace, int64_t workspace_bytes, int32_t n_threads);
-const char *linear_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C, const float *X);
-const char *linear_backward_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,
-                                        const float *X);
-int launch_linear_f32(const float *X, int64_t ldx, const float *W, const float *b, float *Y,
-                      int64_t ldy, int64_t M, int64_t K, int64_t C, hipStream_t stream);
-const char *linear_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C, const void *X,
-                                   int32_t x_dtype);
-int launch_linear_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *W, const float *b,
-                      float *Y, int64_t ldy, int64_t M, int64_t K, int64_t C, hipStream_t stream);
-const char *linear_backward_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,
-                                            const void *X, int32_t x_dtype);
-int64_t linear_backward_x16_workspace_bytes(int64_t M, int64_t K, int64_t C);
-int linear_backward_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *dY, int64_t ldd,
-                        int64_t M, int64_t K, int64_t C, float *dW, float *db, void *ws,
-                        int64_t ws_bytes, hipStream_t s);
-int64_t plan_sorted_workspace(int64_t n_rows);
-int plan_sorted(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
-                int32_t hub_threshold, int32_t *plan, void *workspace, int64_t workspace_bytes,
-                int64_t *counts_host, hipStream_t stream);
-int plan_sorted_ex(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
-                   int32_t hub_threshold, int32_t *plan, void *workspace,
-                   int64_t workspace_bytes, int64_t *counts_host, hipStream_t stream);
-int plan_sorted_ex2(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
-                    int32_t hub_threshold, int32_t *plan, void *workspace,
-                    int64_t workspace_bytes, int64_t *counts_host, hipStream_t stream);
-int64_t colsplit_workspace(int64_t n_rows, int32_t groups);
-int colsplit(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n_rows,
-             int64_t n_cols, int32_t groups, const int32_t *cuts_host, int32_t *row_ptrs,
-             int32_t *col_out, float *val_out, void *workspace, int64_t workspace_bytes,
-             hipStream_t stream);
-int colsplit_ex(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n_rows,
-                int64_t n_cols, int32_t groups, const int32_t *cuts_host, int32_t whole_rows,
-                int32_t *row_ptrs, int32_t *col_out, float *val_out, void *workspace,
-                int64_t workspace_bytes, hipStream_t stream);
-int colsplit_ex2(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
-                 int64_t n_rows, int64_t n_cols, int32_t groups, const int32_t *cuts_host,
-                 int32_t whole_rows, int32_t coarse_rows, int32_t coarse_groups,
-                 int32_t *row_ptrs, int32_t *col_out, float *val_out, void *workspace,
-                 int64_t workspace_bytes, hipStream_t stream);
-int mgpu_init(int ndev, const int *devices);
-int mgpu_finalize();
-int mgpu_attach(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n,
-                int64_t nnz, hipStream_t stream, int64_t *handle);
-int mgpu_detach(int64_t handle);
-int mgpu_propagate(int64_t handle, const float *X, int64_t ldx, float *Y, int64_t ldy, int64_t F,
-                   int32_t K, hipStream_t stream);
-int64_t lbfgs_workspace(int64_t n, int32_t history_size);
-int lbfgs_init(void *state, int64_t bytes, int64_t n, int32_t history_size, hipStream_t s);
-int lbfgs_begin_step(void *state, hipStream_t s);
-int lbfgs_iterate(void *state, int32_t n_tensors, float *const *params, const float *const *grads,
-                  const int64_t *numels, const float *loss, double lr, int32_t max_iter,
-                  int32_t max_eval, double tol_grad, double tol_change, hipStream_t s);
-int lbfgs_read_status(const void *state, int64_t *out_host, hipStream_t s);
-int64_t train_lbfgs_workspace(int64_t M, int64_t K, int64_t C);
-int train_lbfgs(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels, int64_t M,
-                int64_t K, int64_t C, void *state, int32_t steps, double lr, int32_t max_iter,
-                int32_t max_eval, double tol_grad, double tol_change, float *loss_trace,
-                int64_t *status_trace, void *ws, int64_t ws_bytes, hipStream_t s);
-extern int g_adam_kernel, g_adam_kernel_last;
-int adam_set_tuning(int64_t value);
-int64_t adam_small_max_rows();
-int adam_step(int32_t n_tensors, float *const *params, const float *const *grads,
-              float *const *exp_avgs, float *const *exp_avg_sqs, const int64_t *numels,
-              int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
-              hipStream_t s);
-int64_t train_adam_workspace(int64_t M, int64_t K, int64_t C);
-int train_adam(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels, int64_t M,
-               int64_t K, int64_t C, float *mW, float *vW, float *mb, float *vb, int64_t step0,
-               int32_t epochs, double lr, double beta1, double beta2, double eps,
-               double weight_decay, float *loss_trace, void *ws, int64_t ws_bytes, hipStream_t s);
-hipError_t warm_adam(hipStream_t);
 
 }  // namespace sgc
 
@@ -283,31 +129,47 @@ int sgc_plan_build(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
                       plan_capacity, n_heavy_host, n_hub_host, as_stream(stream));
 }
 
+// The SpMM flag bits an entry point accepts, and the one check of them.
+static constexpr uint32_t kSpmmFlags =
+    SGC_SPMM_X_PADDED | SGC_SPMM_Y_PADDED | SGC_SPMM_NO_HUB | SGC_SPMM_HUB_ONLY |
+    SGC_SPMM_ACCUMULATE | SGC_SPMM_HUB_SERIAL | SGC_SPMM_LIGHT_ORDER | SGC_SPMM_X_UNDER_4G;
+
+static int check_spmm_flags(uint32_t flags, const char *who) {
+    SGC_REQUIRE((flags & ~kSpmmFlags) == 0, SGC_EINVAL, "%s: unknown flags 0x%x", who, flags);
+    SGC_REQUIRE(!((flags & SGC_SPMM_NO_HUB) && (flags & SGC_SPMM_HUB_ONLY)), SGC_EINVAL,
+                "%s: NO_HUB and HUB_ONLY together", who);
+    return SGC_OK;
+}
+
+// The call every exported generation fills: without a plan its counts are
+// neutral (0 heavy / hub rows, -1 = unknown non-empty and not-wide counts).
+static SpmmCall spmm_call(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
+                          int64_t row_begin, int64_t row_end, const float *X, int64_t ldx,
+                          float *Y, int64_t ldy, int64_t F, const int32_t *plan, int64_t n_heavy,
+                          int64_t n_hub, int32_t heavy_threshold, uint32_t flags,
+                          int64_t n_nonempty = -1, int64_t n_not_wide = -1,
+                          int32_t wide_max_nnz = 0) {
+    return SpmmCall{row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F, plan,
+                    plan ? n_heavy : 0, plan ? n_hub : 0, heavy_threshold, flags,
+                    plan ? n_nonempty : -1, plan ? n_not_wide : -1, wide_max_nnz};
+}
+
 int sgc_spmm_csr_f32(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
                      int64_t row_begin, int64_t row_end, const float *X, int64_t ldx, float *Y,
                      int64_t ldy, int64_t F, const int32_t *plan, int64_t n_heavy,
                      int64_t n_hub, int32_t heavy_threshold, void *stream) {
-    return launch_spmm(row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F, plan,
-                       plan ? n_heavy : 0, plan ? n_hub : 0, heavy_threshold, 0u,
+    return launch_spmm(spmm_call(row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F,
+                                 plan, n_heavy, n_hub, heavy_threshold, 0u),
                        as_stream(stream));
 }
-
-static constexpr uint32_t kSpmmFlags =
-    SGC_SPMM_X_PADDED | SGC_SPMM_Y_PADDED | SGC_SPMM_NO_HUB | SGC_SPMM_HUB_ONLY |
-    SGC_SPMM_ACCUMULATE | SGC_SPMM_HUB_SERIAL | SGC_SPMM_LIGHT_ORDER | SGC_SPMM_X_UNDER_4G;
 
 int sgc_spmm_csr_f32_ex(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
                         int64_t row_begin, int64_t row_end, const float *X, int64_t ldx, float *Y,
                         int64_t ldy, int64_t F, const int32_t *plan, int64_t n_heavy,
                         int64_t n_hub, int32_t heavy_threshold, uint32_t flags, void *stream) {
-    constexpr uint32_t known = SGC_SPMM_X_PADDED | SGC_SPMM_Y_PADDED | SGC_SPMM_NO_HUB |
-                               SGC_SPMM_HUB_ONLY | SGC_SPMM_ACCUMULATE | SGC_SPMM_HUB_SERIAL |
-                               SGC_SPMM_LIGHT_ORDER | SGC_SPMM_X_UNDER_4G;
-    SGC_REQUIRE((flags & ~known) == 0, SGC_EINVAL, "spmm_ex: unknown flags 0x%x", flags);
-    SGC_REQUIRE(!((flags & SGC_SPMM_NO_HUB) && (flags & SGC_SPMM_HUB_ONLY)), SGC_EINVAL,
-                "spmm_ex: NO_HUB and HUB_ONLY together");
-    return launch_spmm(row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F, plan,
-                       plan ? n_heavy : 0, plan ? n_hub : 0, heavy_threshold, flags,
+    if (const int rc = check_spmm_flags(flags, "spmm_ex")) return rc;
+    return launch_spmm(spmm_call(row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F,
+                                 plan, n_heavy, n_hub, heavy_threshold, flags),
                        as_stream(stream));
 }
 
@@ -316,12 +178,10 @@ int sgc_spmm_csr_f32_ex2(const int32_t *row_ptr, const int32_t *col_idx, const f
                          float *Y, int64_t ldy, int64_t F, const int32_t *plan, int64_t n_heavy,
                          int64_t n_hub, int32_t heavy_threshold, uint32_t flags,
                          int64_t n_nonempty, void *stream) {
-    SGC_REQUIRE((flags & ~kSpmmFlags) == 0, SGC_EINVAL, "spmm_ex2: unknown flags 0x%x", flags);
-    SGC_REQUIRE(!((flags & SGC_SPMM_NO_HUB) && (flags & SGC_SPMM_HUB_ONLY)), SGC_EINVAL,
-                "spmm_ex2: NO_HUB and HUB_ONLY together");
-    return launch_spmm(row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F, plan,
-                       plan ? n_heavy : 0, plan ? n_hub : 0, heavy_threshold, flags,
-                       as_stream(stream), plan ? n_nonempty : -1);
+    if (const int rc = check_spmm_flags(flags, "spmm_ex2")) return rc;
+    return launch_spmm(spmm_call(row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F,
+                                 plan, n_heavy, n_hub, heavy_threshold, flags, n_nonempty),
+                       as_stream(stream));
 }
 
 int sgc_spmm_csr_f32_ex3(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
@@ -330,13 +190,23 @@ int sgc_spmm_csr_f32_ex3(const int32_t *row_ptr, const int32_t *col_idx, const f
                          int64_t n_hub, int32_t heavy_threshold, uint32_t flags,
                          int64_t n_nonempty, int64_t n_not_wide, int32_t wide_max_nnz,
                          void *stream) {
-    SGC_REQUIRE((flags & ~kSpmmFlags) == 0, SGC_EINVAL, "spmm_ex3: unknown flags 0x%x", flags);
-    SGC_REQUIRE(!((flags & SGC_SPMM_NO_HUB) && (flags & SGC_SPMM_HUB_ONLY)), SGC_EINVAL,
-                "spmm_ex3: NO_HUB and HUB_ONLY together");
-    return launch_spmm(row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F, plan,
-                       plan ? n_heavy : 0, plan ? n_hub : 0, heavy_threshold, flags,
-                       as_stream(stream), plan ? n_nonempty : -1, plan ? n_not_wide : -1,
-                       wide_max_nnz);
+    if (const int rc = check_spmm_flags(flags, "spmm_ex3")) return rc;
+    return launch_spmm(spmm_call(row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F,
+                                 plan, n_heavy, n_hub, heavy_threshold, flags, n_nonempty,
+                                 n_not_wide, wide_max_nnz),
+                       as_stream(stream));
+}
+
+const char *sgc_spmm_kernel_name(int64_t row_begin, int64_t row_end, const float *X, int64_t ldx,
+                                 const float *Y, int64_t ldy, int64_t F, const int32_t *plan,
+                                 int64_t n_heavy, int64_t n_hub, int32_t heavy_threshold,
+                                 uint32_t flags, int64_t n_nonempty, int64_t n_not_wide,
+                                 int32_t wide_max_nnz) {
+    if (check_spmm_flags(flags, "spmm_kernel_name") != SGC_OK) return "none";
+    return spmm_kernel_name(spmm_call(nullptr, nullptr, nullptr, row_begin, row_end, X, ldx,
+                                      const_cast<float *>(Y), ldy, F, plan, n_heavy, n_hub,
+                                      heavy_threshold, flags, n_nonempty, n_not_wide,
+                                      wide_max_nnz));
 }
 
 int sgc_spmm_csr_x16(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
@@ -344,12 +214,7 @@ int sgc_spmm_csr_x16(const int32_t *row_ptr, const int32_t *col_idx, const float
                      int64_t ldx, void *Y, int32_t y_dtype, int64_t ldy, int64_t F,
                      const int32_t *plan, int64_t n_heavy, int64_t n_hub,
                      int32_t heavy_threshold, uint32_t flags, void *stream) {
-    constexpr uint32_t known = SGC_SPMM_X_PADDED | SGC_SPMM_Y_PADDED | SGC_SPMM_NO_HUB |
-                               SGC_SPMM_HUB_ONLY | SGC_SPMM_ACCUMULATE | SGC_SPMM_HUB_SERIAL |
-                               SGC_SPMM_LIGHT_ORDER | SGC_SPMM_X_UNDER_4G;
-    SGC_REQUIRE((flags & ~known) == 0, SGC_EINVAL, "spmm_x16: unknown flags 0x%x", flags);
-    SGC_REQUIRE(!((flags & SGC_SPMM_NO_HUB) && (flags & SGC_SPMM_HUB_ONLY)), SGC_EINVAL,
-                "spmm_x16: NO_HUB and HUB_ONLY together");
+    if (const int rc = check_spmm_flags(flags, "spmm_x16")) return rc;
     return launch_spmm_x16(row_ptr, col_idx, val, row_begin, row_end, X, x_dtype, ldx, Y, y_dtype,
                            ldy, F, plan, plan ? n_heavy : 0, plan ? n_hub : 0, heavy_threshold,
                            flags, as_stream(stream));
@@ -412,22 +277,9 @@ namespace sgc {
 namespace {
 
 struct ListOp {
-    int kind;  // 0 spmm (launch_spmm), 1 pad rows (launch_pad_rows)
-    const int32_t *row_ptr, *col_idx;
-    const float *val;
-    int64_t row_begin, row_end;
-    const float *X;
-    int64_t ldx;
-    float *Y;
-    int64_t ldy, F;
-    const int32_t *plan;
-    int64_t n_heavy, n_hub;
-    int32_t threshold;
-    uint32_t flags;
+    int kind;    // 0 spmm (launch_spmm), 1 pad rows (launch_pad_rows: X = src, Y = dst, row_end rows)
+    SpmmCall c;  // X / Y as recorded
     int32_t x_slot, y_slot;  // SGC_SLOT_*: the pointer as recorded, or the run's X_0 / X_K
-    int64_t n_nonempty = -1;  // the plan's rows with nonzeros (sgc_spmm_csr_f32_ex2), -1 unknown
-    int64_t n_not_wide = -1;  // its light rows above wide_max_nnz (sgc_spmm_csr_f32_ex3), -1 none
-    int32_t wide_max_nnz = 0;
 };
 
 struct LaunchList {
@@ -487,15 +339,11 @@ int sgc_launch_list_add_spmm(int64_t handle, const int32_t *row_ptr, const int32
                              int64_t ldx, float *Y, int64_t ldy, int64_t F, const int32_t *plan,
                              int64_t n_heavy, int64_t n_hub, int32_t heavy_threshold,
                              uint32_t flags, int32_t x_slot, int32_t y_slot) {
-    constexpr uint32_t known = SGC_SPMM_X_PADDED | SGC_SPMM_Y_PADDED | SGC_SPMM_NO_HUB |
-                               SGC_SPMM_HUB_ONLY | SGC_SPMM_ACCUMULATE | SGC_SPMM_HUB_SERIAL |
-                               SGC_SPMM_LIGHT_ORDER | SGC_SPMM_X_UNDER_4G;
-    SGC_REQUIRE((flags & ~known) == 0, SGC_EINVAL, "launch_list_add_spmm: unknown flags 0x%x", flags);
-    SGC_REQUIRE(!((flags & SGC_SPMM_NO_HUB) && (flags & SGC_SPMM_HUB_ONLY)), SGC_EINVAL,
-                "launch_list_add_spmm: NO_HUB and HUB_ONLY together");
-    return list_add(handle, ListOp{0, row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F,
-                                   plan, plan ? n_heavy : 0, plan ? n_hub : 0, heavy_threshold,
-                                   flags, x_slot, y_slot});
+    if (const int rc = check_spmm_flags(flags, "launch_list_add_spmm")) return rc;
+    return list_add(handle, ListOp{0, spmm_call(row_ptr, col_idx, val, row_begin, row_end, X, ldx,
+                                                Y, ldy, F, plan, n_heavy, n_hub, heavy_threshold,
+                                                flags),
+                                   x_slot, y_slot});
 }
 
 int sgc_launch_list_add_spmm_ex2(int64_t handle, const int32_t *row_ptr, const int32_t *col_idx,
@@ -504,14 +352,11 @@ int sgc_launch_list_add_spmm_ex2(int64_t handle, const int32_t *row_ptr, const i
                                  const int32_t *plan, int64_t n_heavy, int64_t n_hub,
                                  int32_t heavy_threshold, uint32_t flags, int64_t n_nonempty,
                                  int32_t x_slot, int32_t y_slot) {
-    SGC_REQUIRE((flags & ~kSpmmFlags) == 0, SGC_EINVAL,
-                "launch_list_add_spmm: unknown flags 0x%x", flags);
-    SGC_REQUIRE(!((flags & SGC_SPMM_NO_HUB) && (flags & SGC_SPMM_HUB_ONLY)), SGC_EINVAL,
-                "launch_list_add_spmm: NO_HUB and HUB_ONLY together");
-    ListOp op{0, row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F, plan,
-              plan ? n_heavy : 0, plan ? n_hub : 0, heavy_threshold, flags, x_slot, y_slot};
-    op.n_nonempty = plan ? n_nonempty : -1;
-    return list_add(handle, op);
+    if (const int rc = check_spmm_flags(flags, "launch_list_add_spmm")) return rc;
+    return list_add(handle, ListOp{0, spmm_call(row_ptr, col_idx, val, row_begin, row_end, X, ldx,
+                                                Y, ldy, F, plan, n_heavy, n_hub, heavy_threshold,
+                                                flags, n_nonempty),
+                                   x_slot, y_slot});
 }
 
 int sgc_launch_list_add_spmm_ex3(int64_t handle, const int32_t *row_ptr, const int32_t *col_idx,
@@ -521,23 +366,19 @@ int sgc_launch_list_add_spmm_ex3(int64_t handle, const int32_t *row_ptr, const i
                                  int32_t heavy_threshold, uint32_t flags, int64_t n_nonempty,
                                  int64_t n_not_wide, int32_t wide_max_nnz, int32_t x_slot,
                                  int32_t y_slot) {
-    SGC_REQUIRE((flags & ~kSpmmFlags) == 0, SGC_EINVAL,
-                "launch_list_add_spmm: unknown flags 0x%x", flags);
-    SGC_REQUIRE(!((flags & SGC_SPMM_NO_HUB) && (flags & SGC_SPMM_HUB_ONLY)), SGC_EINVAL,
-                "launch_list_add_spmm: NO_HUB and HUB_ONLY together");
-    ListOp op{0, row_ptr, col_idx, val, row_begin, row_end, X, ldx, Y, ldy, F, plan,
-              plan ? n_heavy : 0, plan ? n_hub : 0, heavy_threshold, flags, x_slot, y_slot};
-    op.n_nonempty = plan ? n_nonempty : -1;
-    op.n_not_wide = plan ? n_not_wide : -1;
-    op.wide_max_nnz = wide_max_nnz;
-    return list_add(handle, op);
+    if (const int rc = check_spmm_flags(flags, "launch_list_add_spmm")) return rc;
+    return list_add(handle, ListOp{0, spmm_call(row_ptr, col_idx, val, row_begin, row_end, X, ldx,
+                                                Y, ldy, F, plan, n_heavy, n_hub, heavy_threshold,
+                                                flags, n_nonempty, n_not_wide, wide_max_nnz),
+                                   x_slot, y_slot});
 }
 
 int sgc_launch_list_add_pad_rows(int64_t handle, const float *src, int64_t lds, float *dst,
                                  int64_t ldd, int64_t n_rows, int64_t F, int32_t src_slot,
                                  int32_t dst_slot) {
-    return list_add(handle, ListOp{1, nullptr, nullptr, nullptr, 0, n_rows, src, lds, dst, ldd, F,
-                                   nullptr, 0, 0, 0, 0u, src_slot, dst_slot});
+    return list_add(handle, ListOp{1, SpmmCall{nullptr, nullptr, nullptr, 0, n_rows, src, lds, dst,
+                                               ldd, F, nullptr, 0, 0, 0, 0u},
+                                   src_slot, dst_slot});
 }
 
 int sgc_launch_list_run(int64_t handle, const float *X0, float *out, void *stream) {
@@ -558,18 +399,16 @@ int sgc_launch_list_run(int64_t handle, const float *X0, float *out, void *strea
     hipStream_t s = as_stream(stream);
     int rc = SGC_OK;
     for (const ListOp &op : L->ops) {
-        const float *x = slot_ptr(op.X, op.x_slot, X0, out);
-        float *y = slot_ptr(op.Y, op.y_slot, X0, out);
-        if (!x || !y) {
+        SpmmCall c = op.c;
+        c.X = slot_ptr(c.X, op.x_slot, X0, out);
+        c.Y = slot_ptr(c.Y, op.y_slot, X0, out);
+        if (!c.X || !c.Y) {
             set_error("launch_list_run: null X_0 / X_K for a slot");
             rc = SGC_EINVAL;
             break;
         }
-        rc = op.kind == 0 ? launch_spmm(op.row_ptr, op.col_idx, op.val, op.row_begin, op.row_end, x,
-                                        op.ldx, y, op.ldy, op.F, op.plan, op.n_heavy, op.n_hub,
-                                        op.threshold, op.flags, s, op.n_nonempty, op.n_not_wide,
-                                        op.wide_max_nnz)
-                          : launch_pad_rows(x, op.ldx, y, op.ldy, op.row_end, op.F, s);
+        rc = op.kind == 0 ? launch_spmm(c, s)
+                          : launch_pad_rows(c.X, c.ldx, c.Y, c.ldy, c.row_end, c.F, s);
         if (rc != SGC_OK) break;
     }
     if (cur != L->device) (void)hipSetDevice(cur);
@@ -632,13 +471,12 @@ int sgc_propagate_groups_f32_ex3(int32_t groups, const int32_t *row_ptrs, const 
             const int32_t *plan = plans_host ? plans_host[g] : nullptr;
             const uint32_t gf = fl | (g ? (uint32_t)SGC_SPMM_ACCUMULATE : 0u) |
                                 (plan && plan_flags_host ? plan_flags_host[g] : 0u);
-            const int rc = launch_spmm(row_ptrs + (int64_t)g * (n_rows + 1), col_idx, val, 0,
-                                       n_rows, src, lds, dst, ldd, F, plan,
-                                       plan ? n_heavy_host[g] : 0, plan ? n_hub_host[g] : 0,
-                                       plan ? thresholds_host[g] : 0, gf, s,
-                                       plan && n_nonempty_host ? n_nonempty_host[g] : -1,
-                                       plan && n_not_wide_host ? n_not_wide_host[g] : -1,
-                                       wide_max_nnz);
+            const int rc = launch_spmm(
+                spmm_call(row_ptrs + (int64_t)g * (n_rows + 1), col_idx, val, 0, n_rows, src, lds,
+                          dst, ldd, F, plan, plan ? n_heavy_host[g] : 0, plan ? n_hub_host[g] : 0,
+                          plan ? thresholds_host[g] : 0, gf, n_nonempty_host ? n_nonempty_host[g] : -1,
+                          n_not_wide_host ? n_not_wide_host[g] : -1, wide_max_nnz),
+                s);
             if (rc) return rc;
         }
         src = dst;
@@ -916,20 +754,23 @@ int64_t sgc_colsplit_workspace(int64_t n_rows, int32_t groups) {
     return colsplit_workspace(n_rows, groups);
 }
 
+// the pure split: every row cut at the column cuts (whole_rows = 0)
 int sgc_csr_colsplit(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
                      int64_t n_rows, int64_t n_cols, int32_t groups, const int32_t *cuts_host,
                      int32_t *row_ptrs, int32_t *col_out, float *val_out, void *workspace,
                      int64_t workspace_bytes, void *stream) {
-    return colsplit(row_ptr, col_idx, val, n_rows, n_cols, groups, cuts_host, row_ptrs, col_out,
-                    val_out, workspace, workspace_bytes, as_stream(stream));
+    return colsplit(row_ptr, col_idx, val, n_rows, n_cols, groups, cuts_host, 0, 0, groups,
+                    row_ptrs, col_out, val_out, workspace, workspace_bytes, as_stream(stream));
 }
 
+// every row above whole_rows cut at all the cuts (coarse_groups = groups)
 int sgc_csr_colsplit_ex(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
                         int64_t n_rows, int64_t n_cols, int32_t groups, const int32_t *cuts_host,
                         int32_t whole_rows, int32_t *row_ptrs, int32_t *col_out, float *val_out,
                         void *workspace, int64_t workspace_bytes, void *stream) {
-    return colsplit_ex(row_ptr, col_idx, val, n_rows, n_cols, groups, cuts_host, whole_rows,
-                       row_ptrs, col_out, val_out, workspace, workspace_bytes, as_stream(stream));
+    return colsplit(row_ptr, col_idx, val, n_rows, n_cols, groups, cuts_host, whole_rows,
+                    whole_rows, groups, row_ptrs, col_out, val_out, workspace, workspace_bytes,
+                    as_stream(stream));
 }
 
 int sgc_csr_colsplit_ex2(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
@@ -937,30 +778,43 @@ int sgc_csr_colsplit_ex2(const int32_t *row_ptr, const int32_t *col_idx, const f
                          const int32_t *cuts_host, int32_t whole_rows, int32_t coarse_rows,
                          int32_t coarse_groups, int32_t *row_ptrs, int32_t *col_out,
                          float *val_out, void *workspace, int64_t workspace_bytes, void *stream) {
-    return colsplit_ex2(row_ptr, col_idx, val, n_rows, n_cols, groups, cuts_host, whole_rows,
-                        coarse_rows, coarse_groups, row_ptrs, col_out, val_out, workspace,
-                        workspace_bytes, as_stream(stream));
+    return colsplit(row_ptr, col_idx, val, n_rows, n_cols, groups, cuts_host, whole_rows,
+                    coarse_rows, coarse_groups, row_ptrs, col_out, val_out, workspace,
+                    workspace_bytes, as_stream(stream));
 }
 
 int64_t sgc_plan_sorted_workspace(int64_t n_rows) { return plan_sorted_workspace(n_rows); }
 
+// the first n_counts of plan_sorted's counts: 3 (heavy, hub, longest row), 4 or all 8
+static int plan_sorted_counts(int n_counts, const int32_t *row_ptr, int64_t row_begin,
+                              int64_t row_end, int32_t threshold, int32_t hub_threshold,
+                              int32_t *plan, void *workspace, int64_t workspace_bytes,
+                              int64_t *counts_host, void *stream) {
+    SGC_REQUIRE(counts_host, SGC_EINVAL, "plan_sorted: null pointer");
+    int64_t c[kPlanSortedCounts] = {};
+    const int rc = plan_sorted(row_ptr, row_begin, row_end, threshold, hub_threshold, plan,
+                               workspace, workspace_bytes, c, as_stream(stream));
+    for (int i = 0; i < n_counts; ++i) counts_host[i] = c[i];
+    return rc;
+}
+
 int sgc_plan_sorted(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
                     int32_t threshold, int32_t hub_threshold, int32_t *plan, void *workspace,
                     int64_t workspace_bytes, int64_t *counts_host, void *stream) {
-    return plan_sorted(row_ptr, row_begin, row_end, threshold, hub_threshold, plan, workspace,
-                       workspace_bytes, counts_host, as_stream(stream));
-}
-
-int sgc_plan_sorted_ex2(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
-                        int32_t threshold, int32_t hub_threshold, int32_t *plan, void *workspace,
-                        int64_t workspace_bytes, int64_t *counts_host, void *stream) {
-    return plan_sorted_ex2(row_ptr, row_begin, row_end, threshold, hub_threshold, plan, workspace,
-                           workspace_bytes, counts_host, as_stream(stream));
+    return plan_sorted_counts(3, row_ptr, row_begin, row_end, threshold, hub_threshold, plan,
+                              workspace, workspace_bytes, counts_host, stream);
 }
 
 int sgc_plan_sorted_ex(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
                        int32_t threshold, int32_t hub_threshold, int32_t *plan, void *workspace,
                        int64_t workspace_bytes, int64_t *counts_host, void *stream) {
-    return plan_sorted_ex(row_ptr, row_begin, row_end, threshold, hub_threshold, plan, workspace,
-                          workspace_bytes, counts_host, as_stream(stream));
+    return plan_sorted_counts(4, row_ptr, row_begin, row_end, threshold, hub_threshold, plan,
+                              workspace, workspace_bytes, counts_host, stream);
+}
+
+int sgc_plan_sorted_ex2(const int32_t *row_ptr, int64_t row_begin, int64_t row_end,
+                        int32_t threshold, int32_t hub_threshold, int32_t *plan, void *workspace,
+                        int64_t workspace_bytes, int64_t *counts_host, void *stream) {
+    return plan_sorted_counts(kPlanSortedCounts, row_ptr, row_begin, row_end, threshold,
+                              hub_threshold, plan, workspace, workspace_bytes, counts_host, stream);
 }

@@ -43,35 +43,12 @@ static constexpr int kWave = 64;  // CDNA wavefront width (never 32)
         hipLaunchKernelGGL(name##_kernel, dim3(1), dim3(kWave), 0, s);      \
         return hipGetLastError();                                           \
     }
-hipError_t warm_spmm(hipStream_t);
-hipError_t warm_side_streams();  // creates the SpMM's per-device side-stream pool
-hipError_t warm_ingest(hipStream_t);
-hipError_t warm_plan(hipStream_t);
-hipError_t warm_sort(hipStream_t);
-hipError_t warm_groups(hipStream_t);
-hipError_t warm_exchange(hipStream_t);
-hipError_t warm_linear(hipStream_t);
-hipError_t warm_xent(hipStream_t);
-hipError_t warm_xent_fwd_stop(hipStream_t);
-hipError_t warm_loss(hipStream_t);
-hipError_t warm_lbfgs(hipStream_t);
-hipError_t warm_normalize(hipStream_t);
-hipError_t warm_subgraph(hipStream_t);
+// (each unit's warm-up is declared in internal.h)
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // V consecutive fp32 in one lane: float / float2 / float4 register vectors,
 // loaded with one global_load_dword{,x2,x4}.
-// LDS image depth of the classifier tile (gemm_tile.h; linear.hip defines it,
-// sgc_set_tuning("tile_buffers") sets it: 1 or 2).
-extern int g_tile_buffers;
-// Classifier forward kernel (linear.hip): 0 auto, 1 LDS tile, 2 streaming.
-extern int g_linear_kernel;
-// k per chunk of the streaming classifier kernel (32 or 64).
-extern int g_linear_ck;
-// Classifier weight backward: 0 auto, 1 fp32 MFMA slabs, 2 split-bf16 slabs (xent.hip).
-extern int g_backward_kernel;
-
 template <int V> struct Vec { typedef float __attribute__((ext_vector_type(V))) T; };
 template <> struct Vec<1> { typedef float T; };
 

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "common.h"
+#include "internal.h"
 
 #if !defined(__HIP_DEVICE_COMPILE__)
 

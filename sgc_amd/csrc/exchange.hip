@@ -23,6 +23,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "internal.h"
 
 namespace sgc {
 

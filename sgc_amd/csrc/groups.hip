@@ -48,6 +48,7 @@
 // propagate.GROUP_LADDER_RULE; column_groups_rule below and the callers that
 // split S by it keep the size rule's G for every row above T.
 #include "common.h"
+#include "internal.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -211,11 +212,12 @@ int64_t colsplit_workspace(int64_t n_rows, int32_t groups) {
                      up((size_t)groups * nblocks(n_rows) * sizeof(int32_t)));
 }
 
-int colsplit_ex2(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
-                 int64_t n_rows, int64_t n_cols, int32_t groups, const int32_t *cuts_host,
-                 int32_t whole_rows, int32_t coarse_rows, int32_t coarse_groups,
-                 int32_t *row_ptrs, int32_t *col_out, float *val_out, void *workspace,
-                 int64_t workspace_bytes, hipStream_t stream) {
+// (sgc_csr_colsplit_ex2's arguments; the narrower exported forms pass
+// coarse_rows = whole_rows, coarse_groups = groups, and whole_rows = 0)
+int colsplit(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n_rows,
+             int64_t n_cols, int32_t groups, const int32_t *cuts_host, int32_t whole_rows,
+             int32_t coarse_rows, int32_t coarse_groups, int32_t *row_ptrs, int32_t *col_out,
+             float *val_out, void *workspace, int64_t workspace_bytes, hipStream_t stream) {
     SGC_REQUIRE(whole_rows >= 0, SGC_EINVAL, "colsplit: whole_rows must be >= 0");
     SGC_REQUIRE(groups >= 1 && groups <= kGroupsMax, SGC_EINVAL,
                 "colsplit: groups must be 1..%d", kGroupsMax);
@@ -268,25 +270,6 @@ int colsplit_ex2(const int32_t *row_ptr, const int32_t *col_idx, const float *va
                        col_out, val_out);
     SGC_HIP_CHECK(hipGetLastError());
     return SGC_OK;
-}
-
-// every row above whole_rows cut at all the cuts (coarse_groups = groups)
-int colsplit_ex(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n_rows,
-                int64_t n_cols, int32_t groups, const int32_t *cuts_host, int32_t whole_rows,
-                int32_t *row_ptrs, int32_t *col_out, float *val_out, void *workspace,
-                int64_t workspace_bytes, hipStream_t stream) {
-    return colsplit_ex2(row_ptr, col_idx, val, n_rows, n_cols, groups, cuts_host, whole_rows,
-                        whole_rows, groups, row_ptrs, col_out, val_out, workspace,
-                        workspace_bytes, stream);
-}
-
-// the pure split: every row cut at the column cuts (whole_rows = 0)
-int colsplit(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n_rows,
-             int64_t n_cols, int32_t groups, const int32_t *cuts_host, int32_t *row_ptrs,
-             int32_t *col_out, float *val_out, void *workspace, int64_t workspace_bytes,
-             hipStream_t stream) {
-    return colsplit_ex(row_ptr, col_idx, val, n_rows, n_cols, groups, cuts_host, 0, row_ptrs,
-                       col_out, val_out, workspace, workspace_bytes, stream);
 }
 
 // Every row's columns strictly ascending?  (the ingest's status bit 2 for a

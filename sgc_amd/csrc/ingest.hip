@@ -13,7 +13,7 @@
 // row_ptr from the row transitions.  Unsorted input: stable LSD radix sort
 // (the library's own, sort.hip) of (row, position) pairs, then a gather.
 #include "common.h"
-#include "sort.h"
+#include "internal.h"
 
 namespace sgc {
 

@@ -34,6 +34,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "internal.h"
 
 namespace sgc {
 
@@ -570,11 +571,6 @@ int lbfgs_read_status(const void *state, int64_t *out_host, hipStream_t s) {
 // set the stop word, the rest of the step's launches return at entry: nothing
 // moves until the next step's reset.  The first closure of step s runs always
 // (the reset precedes it) and writes its loss straight into loss_trace[s].
-int64_t xent_workspace_bytes(int64_t M, int64_t K, int64_t C);  // xent.hip
-int xent_closure_check(const char *what, int64_t M, int64_t K, int64_t C, int64_t ldx);
-int xent_closure(const int64_t *stop, const float *X, int64_t ldx, const float *W, const float *b,
-                 const int64_t *labels, int64_t M, int64_t K, int64_t C, float *loss, float *dW,
-                 float *db, void *ws, hipStream_t s);
 
 // workspace: gradient [n] | loss | the fused step's workspace, each 256-B aligned
 int64_t train_lbfgs_workspace(int64_t M, int64_t K, int64_t C) {

@@ -16,6 +16,7 @@
 #include <utility>
 
 #include "gemm_tile.h"
+#include "internal.h"
 #include "split_bf16.h"
 
 namespace sgc {

@@ -27,15 +27,11 @@
 #include <algorithm>
 
 #include "gemm_tile.h"
+#include "internal.h"
 #include "split_bf16.h"
 #include "x16.h"
 
 namespace sgc {
-
-hipError_t persistent_setup(const void *kernel, int *cus);  // linear.hip
-// xent.hip: the fixed-order reduction of the dW / db partials
-hipError_t launch_reduce_dw_db(const float *slab, int n_parts, int C, int K, int C16, float *dW,
-                               const float *db_slab, float *db, hipStream_t s);
 
 namespace x16 {
 

@@ -30,6 +30,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "internal.h"
 
 namespace sgc {
 

@@ -30,28 +30,9 @@
 #include <vector>
 
 #include "common.h"
+#include "internal.h"
 
 namespace sgc {
-
-int64_t plan_sorted_workspace(int64_t n_rows);
-int plan_sorted(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
-                int32_t hub_threshold, int32_t *plan, void *workspace, int64_t workspace_bytes,
-                int64_t *counts_host, hipStream_t stream);
-int launch_spmm(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
-                int64_t row_begin, int64_t row_end, const float *X, int64_t ldx, float *Y,
-                int64_t ldy, int64_t F, const int32_t *heavy_rows, int64_t n_heavy,
-                int64_t n_hub, int32_t heavy_threshold, uint32_t flags, hipStream_t stream,
-                int64_t n_nonempty = -1, int64_t n_not_wide = -1, int32_t wide_max_nnz = 0);
-int launch_pad_rows(const float *src, int64_t lds, float *dst, int64_t ldd, int64_t n_rows,
-                    int64_t F, hipStream_t stream);
-int64_t colsplit_workspace(int64_t n_rows, int32_t groups);
-int colsplit(const int32_t *row_ptr, const int32_t *col_idx, const float *val, int64_t n_rows,
-             int64_t n_cols, int32_t groups, const int32_t *cuts_host, int32_t *row_ptrs,
-             int32_t *col_out, float *val_out, void *workspace, int64_t workspace_bytes,
-             hipStream_t stream);
-int csr_cols_ascending(const int32_t *row_ptr, const int32_t *col_idx, int64_t n_rows,
-                       hipStream_t stream, bool *ascending);
-int column_groups_rule(int64_t nnz, int64_t width);
 
 namespace {
 
@@ -231,8 +212,9 @@ int set_for(Graph &g, Replica &r, int G, hipStream_t stream, GroupSet **out) {
         const int64_t ws_bytes = colsplit_workspace(g.n, G);
         void *ws = nullptr;
         SGC_HIP_CHECK(hipMalloc(&ws, (size_t)ws_bytes));
-        int rc = colsplit(r.row_ptr, r.col, r.val, g.n, g.n, G, cuts.data(), gs.row_ptrs, gs.col,
-                          gs.val, ws, ws_bytes, stream);
+        // the pure split: every row cut at the column cuts
+        int rc = colsplit(r.row_ptr, r.col, r.val, g.n, g.n, G, cuts.data(), 0, 0, G, gs.row_ptrs,
+                          gs.col, gs.val, ws, ws_bytes, stream);
         const hipError_t sync = hipStreamSynchronize(stream);
         (void)hipFree(ws);
         if (rc == SGC_OK && sync != hipSuccess) {
@@ -274,7 +256,7 @@ int plans_for(Graph &g, GroupSet &gs, int64_t width, hipStream_t stream,
             rc = SGC_EHIP;
             break;
         }
-        int64_t counts[3] = {0, 0, 0};
+        int64_t counts[kPlanSortedCounts] = {};  // heavy, hub, longest row, ...
         rc = plan_sorted(gs.row_ptrs + (int64_t)k * (g.n + 1), 0, g.n, th, hub, p.rows, ws,
                          ws_bytes, counts, stream);  // synchronous
         p.n_heavy = counts[0];
@@ -508,11 +490,12 @@ int mgpu_propagate(int64_t handle, const float *X, int64_t ldx, float *Y, int64_
                 // column groups: group 0 plain, groups 1.. continue its chains
                 for (int k = 0; k < j.gs->G; ++k) {
                     const Plan &pl = (*j.plans)[k];
-                    rc = launch_spmm(j.gs->row_ptrs + (int64_t)k * (g.n + 1), j.gs->col,
-                                     j.gs->val, 0, g.n, src, j.ld, dst, ldd, j.w, pl.rows,
-                                     pl.n_heavy, pl.n_hub, pl.threshold,
-                                     flags | pl.flags | (k ? (uint32_t)SGC_SPMM_ACCUMULATE : 0u),
-                                     s.stream);
+                    rc = launch_spmm(
+                        SpmmCall{j.gs->row_ptrs + (int64_t)k * (g.n + 1), j.gs->col, j.gs->val, 0,
+                                 g.n, src, j.ld, dst, ldd, j.w, pl.rows, pl.n_heavy, pl.n_hub,
+                                 pl.threshold,
+                                 flags | pl.flags | (k ? (uint32_t)SGC_SPMM_ACCUMULATE : 0u)},
+                        s.stream);
                     if (rc != SGC_OK) return rc;
                 }
                 src = dst;

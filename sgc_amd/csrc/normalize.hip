@@ -30,6 +30,7 @@
 // and a compaction pass (pass 3) removes exactly the marked entries, keeping
 // order.
 #include "common.h"
+#include "internal.h"
 
 #include <hipcub/hipcub.hpp>
 

@@ -12,7 +12,7 @@
 // degree 4,194,303): hipCUB's made this translation unit's code object
 // 2.2 MB, whose load cost the first plan of a process 12-46 ms.
 #include "common.h"
-#include "sort.h"
+#include "internal.h"
 
 namespace sgc {
 
@@ -59,7 +59,7 @@ __global__ void plan_keys_kernel(const int32_t *__restrict__ row_ptr, int row_be
 size_t sort_temp_bytes(int64_t n) { return (size_t)radix_sort_workspace(n); }
 
 constexpr size_t kAlign = 256;
-constexpr int kPlanCounts = 8;  // (one kAlign block, as the four counts were)
+constexpr int kPlanCounts = kPlanSortedCounts;  // (one kAlign block, as the four counts were)
 size_t up(size_t b) { return (b + kAlign - 1) / kAlign * kAlign; }
 
 }  // namespace
@@ -73,8 +73,9 @@ int64_t plan_sorted_workspace(int64_t n_rows) {
 // counts_host[0..3]: rows above threshold, rows above hub_threshold, the
 // longest row's nonzeros, rows with at least one nonzero; [4..7]: rows of
 // more than 4 / 8 / 16 / 32 nonzeros (what a launch with wide items counts
-// its per-slice light rows from)
-int plan_sorted_ex2(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
+// its per-slice light rows from): kPlanSortedCounts entries (the exported
+// sgc_plan_sorted / _ex forms copy the first three / four)
+int plan_sorted(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
                    int32_t hub_threshold, int32_t *plan, void *workspace,
                    int64_t workspace_bytes, int64_t *counts_host, hipStream_t stream) {
     SGC_REQUIRE(row_ptr && plan && counts_host && workspace, SGC_EINVAL, "plan_sorted: null pointer");
@@ -115,32 +116,6 @@ int plan_sorted_ex2(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, 
     if (rc != SGC_OK) return rc;
     SGC_HIP_CHECK(hipStreamSynchronize(stream));
     return SGC_OK;
-}
-
-// the four-count form
-int plan_sorted_ex(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
-                   int32_t hub_threshold, int32_t *plan, void *workspace,
-                   int64_t workspace_bytes, int64_t *counts_host, hipStream_t stream) {
-    SGC_REQUIRE(counts_host, SGC_EINVAL, "plan_sorted: null pointer");
-    int64_t c[kPlanCounts] = {};
-    const int rc = plan_sorted_ex2(row_ptr, row_begin, row_end, threshold, hub_threshold, plan,
-                                   workspace, workspace_bytes, c, stream);
-    for (int i = 0; i < 4; ++i) counts_host[i] = c[i];
-    return rc;
-}
-
-// the three-count form (heavy, hub, longest row)
-int plan_sorted(const int32_t *row_ptr, int64_t row_begin, int64_t row_end, int32_t threshold,
-                int32_t hub_threshold, int32_t *plan, void *workspace, int64_t workspace_bytes,
-                int64_t *counts_host, hipStream_t stream) {
-    SGC_REQUIRE(counts_host, SGC_EINVAL, "plan_sorted: null pointer");
-    int64_t c[4] = {0, 0, 0, 0};
-    const int rc = plan_sorted_ex(row_ptr, row_begin, row_end, threshold, hub_threshold, plan,
-                                  workspace, workspace_bytes, c, stream);
-    counts_host[0] = c[0];
-    counts_host[1] = c[1];
-    counts_host[2] = c[2];
-    return rc;
 }
 
 SGC_WARM_UNIT(warm_plan)

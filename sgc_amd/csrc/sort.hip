@@ -21,7 +21,7 @@
 //            their input order and the pass is stable.
 // Deterministic: no result depends on atomic order (the count's atomics only
 // add).  Descending order compares key_max - key.
-#include "sort.h"
+#include "internal.h"
 
 #include <algorithm>
 

@@ -34,10 +34,13 @@
 // anyway, so the ragged chunk touches no line the result does not need.
 #include "common.h"
 #include "hub.h"
+#include "internal.h"
 #include "lane_lines.h"
+#include "spmm_schedule.h"
 
 #include <algorithm>
 #include <atomic>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <string>
@@ -1201,7 +1204,8 @@ __global__ __launch_bounds__(64 * (NL + 1)) void spmm_hub_kernel(
 
 namespace {
 
-constexpr int kWavesPerBlock = kBlock / kWave;
+static_assert(kSchedWavesPerBlock == kBlock / kWave && kSchedWave == kWave,
+              "spmm_schedule.h sizes its grids for this workgroup");
 
 struct LaunchArgs {
     const int *row_ptr;
@@ -1212,19 +1216,12 @@ struct LaunchArgs {
     float *Y;
     int64_t ldy;
     int row_begin, n_rows, F;
-    const int *heavy_rows;
-    int n_heavy, heavy_threshold;
-    int slices;
+    const int *heavy_rows;  // the light kernel's heavy rows (the hub rows taken off)
+    int heavy_threshold;
     int accum;
     hipStream_t stream;
     const int *light_rows;  // SGC_SPMM_LIGHT_ORDER: the light rows in processing order, or null
-    int n_light;            // light items of that order (an accumulate launch: those with nonzeros)
-    // fused rows + hub launch (spmm_rows_kernel HF = 32): the hub rows and items
-    const int *hub_rows = nullptr;
-    int hub_chunks = 0, n_hub_blocks = 0;
-    // wide items (spmm_rows_kernel WD > 0): the last n_wide of the n_light
-    // light items run as wide waves; wide_first: before the slices' workgroups
-    int n_wide = 0, wide_first = 0;
+    const int *hub_rows;    // the hub rows (spmm_hub_kernel, or the fused items of HF = 32)
 };
 
 // A side stream + fork/join events per (device, caller's stream) for the
@@ -1367,147 +1364,52 @@ struct TimedGuard {
 // vs. an unpipelined U = 16 / 32; profiles/r01_sweep_pipe.log).
 constexpr int kHeavyU = 16;
 
-// Heavy rows, two nonzeros per load instruction (row_pairs_pipe, 16-B lanes)
-// instead of one wave per 64*VH-float sub-chunk (row_chunks_pipe): bit 0 = in
-// the multi-row kernel (Reddit shape K=2: 9.29 -> 9.12 ms, profiles/r03/s1/ab.log),
-// bit 1 = in the one-row kernel; bit 2 = four nonzeros per load instead of two
-// in the multi-row kernel on launches of <= 32 floats (row_quads_pipe); bit 3
-// = the same on 33..64-float launches, transposed (row_quadsT_pipe: one
-// 64-float hop over all Reddit-shape rows 0.715 -> 0.539 ms); bit 4 = the
-// pairs transposed (row_pairs_pipe TR: 76 floats 0.775 -> 0.747 ms, 304
-// floats 2.26 -> 2.16, Reddit K=2 8.11 -> 8.00; profiles/r04/quadsT_ab.log,
-// pairsT_ab.log; all bit-identical).
-// Set through sgc_set_tuning("heavy_pairs").
-static int g_heavy_pairs = 29;
-// One-row kernel: row_chunks_pipe2 (whole-block schedule) on launches of at
-// least this many rows, row_chunks_pipe below.  Measured bit-identical,
-// interleaved (profiles/r03/s5/chunks_*.log): RMAT shape K=3 (4.2 M rows)
-// 95.5 -> 94.1 ms; Pubmed shape K=2 (19.7 k rows, latency-bound) 0.102 ->
-// 0.109 ms.
-constexpr int kChunksPipe2Rows = 1 << 20;
-
 template <int V, int C, int HF = 0>
-hipError_t launch_vc(const LaunchArgs &a) {
+hipError_t launch_vc(const LaunchArgs &a, const SpmmSchedule &s) {
     constexpr int U0 = (C * V >= 16) ? 2 : (C * V >= 8) ? 4 : 8;
     constexpr int U = U0;
     constexpr int UH = kHeavyU;
-    constexpr int VH = (SGC_HEAVY_VEC < V) ? SGC_HEAVY_VEC : V;
-    // light items: every row in row order (non-light rows skip themselves),
-    // accumulate launches too.  Taking an accumulate launch's light rows with
-    // nonzeros from the plan instead (length order, as the multi-row kernel
-    // does) measured slower here: RMAT shape, G = 4, one hop 29.29 -> 31.62 ms
-    // in the pure split and 28.58 -> 28.63 with whole rows of <= 32 nonzeros
-    // (profiles/whole_rows/sweep_rmat_allrows.log) -- a wave per row leaves
-    // nothing to pack, and in row order the partial sums stream.
-    const int64_t waves = (int64_t)a.n_heavy * (C * V / VH) + a.n_rows;
-    const int64_t blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock + (HF ? a.n_hub_blocks : 0);
-    if (blocks >= INT32_MAX) return hipErrorInvalidValue;
-    dim3 grid((unsigned)blocks, (unsigned)a.slices);
-    hipLaunchKernelGGL((spmm_csr_kernel<V, C, U, UH, HF>), grid, dim3(kBlock), 0, a.stream,
-                       a.row_ptr, a.col, a.val, a.X, a.ldx, a.Y, a.ldy, a.row_begin, a.n_rows,
-                       a.F, a.heavy_rows, a.n_heavy, a.heavy_threshold, a.accum,
-                       ((g_heavy_pairs >> 1) & 1) | (a.n_rows >= kChunksPipe2Rows ? 2 : 0),
-                       a.hub_rows, a.hub_chunks, HF ? a.n_hub_blocks : 0);
+    hipLaunchKernelGGL((spmm_csr_kernel<V, C, U, UH, HF>), dim3((unsigned)s.grid_x, (unsigned)s.grid_y),
+                       dim3(kBlock), 0, a.stream, a.row_ptr, a.col, a.val, a.X, a.ldx, a.Y, a.ldy,
+                       a.row_begin, a.n_rows, s.F_load, a.heavy_rows, s.n_heavy, a.heavy_threshold,
+                       a.accum, s.kernel_bits, HF ? a.hub_rows : nullptr, s.fused_chunks,
+                       s.fused_blocks);
     return hipGetLastError();
 }
 
 template <int V, int C>
-hipError_t dispatch_c(int c, const LaunchArgs &a) {
+hipError_t dispatch_c(const LaunchArgs &a, const SpmmSchedule &s) {
     if constexpr (C == 0) {
         return hipErrorInvalidValue;
     } else {
-        if (c == C) return launch_vc<V, C>(a);
-        return dispatch_c<V, C - 1>(c, a);
+        if (s.C == C) return launch_vc<V, C>(a, s);
+        return dispatch_c<V, C - 1>(a, s);
     }
 }
 
-static int g_max_vec = 4;
-
-// Light kernel choice when 16-B lanes are possible (F rounded up to 4 fits
-// the rows and they are 16-B aligned): 0 = auto -- spmm_rows_kernel when
-// spmm_csr_kernel could not use 16-B lanes itself (F % 4 != 0: Reddit's 602)
-// or the launch is narrower than 128 floats or a large one at 128 / > 256
-// floats (kWideRowsMin below), else spmm_csr_kernel (F = 152 .. 256, and
-// Pubmed's 500: its one-row 256-float slices measured faster); 2 / 4 = always
-// spmm_rows_kernel with 32 / 16 lanes per row on wide launches; 1 = never.
-// profiles/r02/sweep_rows*.  Set through sgc_set_tuning("rows_per_wave").
-static int g_rows_per_wave = 0;
-// Large launches with 16-B lanes at F4 == 128 or F4 > 256 take the
-// multi-row kernel (128-float slices, two rows per wave) even when
-// spmm_csr_kernel could use 16-B lanes: one hop over the Reddit-shape graph
-// (interleaved, bit-identical, profiles/r03/s10/ab_reddit.log) at 304 floats
-// (the P = 2 feature block) 3.00 -> 2.50 ms, at 128 1.00 -> 0.94; at 152 / 160
-// the one-row kernel's single 256-float slice stays faster (1.46 vs 1.60), and
-// at 256 it is the RMAT shape's kernel (31.6 vs 37.3 ms per hop).  Small
-// launches (Pubmed shape, F = 500) stay latency-bound on the one-row kernel.
-constexpr int64_t kWideRowsMin = 65536;
-
 template <int LB, int VH, bool O32, int QV, int HF = 0>
-hipError_t launch_rows(const LaunchArgs &a, int F_load, int LR, int vec_store) {
-    const int R = kWave / LR, SW = LR * 4;
-    // each light row stages LB (col, val) pairs in its wave's 64-entry LDS block
-    if (LR <= 0 || R * LB > kWave) return hipErrorInvalidValue;
-    const int slices = (F_load + SW - 1) / SW;
-    // heavy sub-chunks per slice (unpacked heavy rows): whole 64*VH-float
-    // chunks of a slice, or of the launch's width when it is a single slice
-    const int n_sub = (QV > 0 || (g_heavy_pairs & 1)) ? 1
-                      : slices > 1 ? SW / (kWave * VH) : (F_load + kWave * VH - 1) / (kWave * VH);
-    const int64_t heavy_waves = (int64_t)a.n_heavy * n_sub;
-    // light items: every row (non-light rows skip themselves), or with a
-    // light order exactly the light rows (an accumulate launch: the light
-    // rows with nonzeros, the order's head)
-    const int n_light_items = a.light_rows ? a.n_light : a.n_rows;
-    const int64_t waves = heavy_waves + (n_light_items + R - 1) / R;
-    const int64_t blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock + (HF ? a.n_hub_blocks : 0);
-    if (blocks >= INT32_MAX) return hipErrorInvalidValue;
-    if (blocks == 0) return hipSuccess;  // an accumulate launch over empty runs
-    dim3 grid((unsigned)blocks, (unsigned)slices);
-    hipLaunchKernelGGL((spmm_rows_kernel<LB, VH, kHeavyU, O32, QV, HF>), grid, dim3(kBlock), 0,
-                       a.stream, a.row_ptr, a.col, a.val, a.X, a.ldx, a.Y, a.ldy, a.row_begin,
-                       n_light_items, a.F, F_load, LR, vec_store, n_sub, a.heavy_rows, a.n_heavy,
-                       a.heavy_threshold, a.accum, a.light_rows, g_heavy_pairs & 17, a.hub_rows,
-                       a.hub_chunks, HF ? a.n_hub_blocks : 0);
+hipError_t launch_rows(const LaunchArgs &a, const SpmmSchedule &s) {
+    hipLaunchKernelGGL((spmm_rows_kernel<LB, VH, kHeavyU, O32, QV, HF>),
+                       dim3((unsigned)s.grid_x, (unsigned)s.grid_y), dim3(kBlock), 0, a.stream,
+                       a.row_ptr, a.col, a.val, a.X, a.ldx, a.Y, a.ldy, a.row_begin,
+                       s.n_light_items, a.F, s.F_load, s.LR, s.vec_store, s.n_sub, a.heavy_rows,
+                       s.n_heavy, a.heavy_threshold, a.accum, a.light_rows, s.kernel_bits,
+                       HF ? a.hub_rows : nullptr, s.fused_chunks, s.fused_blocks);
     return hipGetLastError();
 }
 
 // The launch with wide items (spmm_rows_kernel WD > 0; LR = 32, a light
-// order, at least two slices): a one-dimensional grid of the slices'
-// workgroups in turn plus the wide waves' workgroups, which replace the
-// per-slice waves of the last a.n_wide light items.
+// order, at least two slices): a one-dimensional grid (spmm_schedule).
 template <int VH, bool O32, int WD>
-hipError_t launch_rows_wide(const LaunchArgs &a, int F_load, int vec_store) {
-    constexpr int LR = 32, R = kWave / LR, SW = LR * 4;
-    const int slices = (F_load + SW - 1) / SW;
-    const int n_sub = (g_heavy_pairs & 1) ? 1 : SW / (kWave * VH);
-    const int n_narrow = a.n_light - a.n_wide;
-    const int64_t waves = (int64_t)a.n_heavy * n_sub + (n_narrow + R - 1) / R;
-    const int64_t slice_blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
-    const int64_t wide_waves = (a.n_wide + R - 1) / R;
-    const int64_t wide_blocks = (wide_waves + kWavesPerBlock - 1) / kWavesPerBlock;
-    const int64_t blocks = slice_blocks * slices + wide_blocks;
-    if (blocks >= INT32_MAX || n_narrow < 0 || !a.light_rows) return hipErrorInvalidValue;
-    if (blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL((spmm_rows_kernel<16, VH, kHeavyU, O32, 0, 0, WD>), dim3((unsigned)blocks),
+hipError_t launch_rows_wide(const LaunchArgs &a, const SpmmSchedule &s) {
+    hipLaunchKernelGGL((spmm_rows_kernel<16, VH, kHeavyU, O32, 0, 0, WD>), dim3((unsigned)s.grid_x),
                        dim3(kBlock), 0, a.stream, a.row_ptr, a.col, a.val, a.X, a.ldx, a.Y, a.ldy,
-                       a.row_begin, n_narrow, a.F, F_load, LR, vec_store, n_sub, a.heavy_rows,
-                       a.n_heavy, a.heavy_threshold, a.accum, a.light_rows, g_heavy_pairs & 17,
-                       nullptr, 0, 0, a.n_wide, (int)wide_blocks, (int)slice_blocks, slices,
-                       a.wide_first);
+                       a.row_begin, s.n_light_items, a.F, s.F_load, s.LR, s.vec_store, s.n_sub,
+                       a.heavy_rows, s.n_heavy, a.heavy_threshold, a.accum, a.light_rows,
+                       s.kernel_bits, nullptr, 0, 0, s.n_wide, (int)s.wide_blocks,
+                       (int)s.slice_blocks, s.slices, s.wide_first);
     return hipGetLastError();
 }
-
-// Largest per-lane register vector the strides and base pointers allow.
-int pick_vec(int64_t F, int64_t ldx, int64_t ldy, const void *X, const void *Y) {
-    for (int V : {4, 2}) {
-        if (V <= g_max_vec && F % V == 0 && ldx % V == 0 && ldy % V == 0 &&
-            reinterpret_cast<uintptr_t>(X) % (4 * V) == 0 &&
-            reinterpret_cast<uintptr_t>(Y) % (4 * V) == 0)
-            return V;
-    }
-    return 1;
-}
-
-constexpr int max_chunks(int V) { return 16 / V; }  // <= 16 accumulators per lane
 
 }  // namespace
 
@@ -1542,143 +1444,52 @@ int join_light_stream(void *side_in, hipStream_t stream) {
     return SGC_OK;
 }
 
-// Feature-slice width in floats (rounded down to whole 64V-float chunks,
-// at least one).  Default 128: one chunk per slice, so the chip's pass over
-// S touches only X[:, slice] -- 119 MB at the Reddit shape, resident in the
-// 256 MB MALL -- at the price of re-reading the CSR once per slice (8 B/nnz).
-// Measured 4.74 ms/hop at the Reddit shape vs 5.48 ms for 256 and 6.24 ms
-// for 0 = one slice as wide as the registers allow (2.9 GB live X)
-// (profiles/r01_sweep_slices.log).  Set through sgc_set_tuning("slice_floats", n).
-static int g_slice_floats = 128;
-// Hub-kernel feature chunk: 0 = auto (32 on 128-B aligned X rows, else 64).
-static int g_hub_chunk = 0;
-// Where the hub kernel runs: 1 = concurrent with the light kernel -- the hub
-// kernel on the caller's stream, the light kernel on a side stream (fork +
-// join events: ~20-30 us of cross-queue synchronisation per launch); 2 = the
-// caller's stream, before the light kernel (serial: costs the hub kernel's
-// own time); 0 = per launch, serial when the caller sets SGC_SPMM_HUB_SERIAL
-// (the Python layer does when the longest hub chain is shorter than that
-// synchronisation: Pubmed shape 70 -> 61 us per hop), else concurrent.
-// Concurrent launches put the HUB kernel on the caller's stream because the
-// stream that waits on the fork event starts a few microseconds later: with
-// the light kernel first, its 256-thread workgroups fill every CU and the
-// 1024-thread hub workgroups trickled in as whole CUs drained, ending up to
-// 0.26 ms after it (profiles/r03/s6 trace); hub first: Reddit K=2 8.96 ->
-// 8.91 ms, one 76-float pass 0.91 -> 0.77 ms (profiles/r03/s7/stream3*.log).
-// Set through sgc_set_tuning("hub_stream").
-static int g_hub_stream = 0;
-// Loader waves per hub workgroup: 15 or 7 (spmm_hub_kernel).  Set through
-// sgc_set_tuning("hub_loaders").
-static int g_hub_loaders = 15;
-// Serial hub rows (SGC_SPMM_HUB_SERIAL) inside the multi-row kernel's launch
-// (spmm_rows_kernel / spmm_csr_kernel HF = 32) instead of a hub kernel launch
-// before it: 1 = on where the launch takes the multi-row kernel over whole
-// 16-B-lane slices or the one-chunk csr kernel.  Set through
-// sgc_set_tuning("hub_fuse").
-static int g_hub_fuse = 1;
-// Wide items (wide_rows_body): light rows of at most Ts nonzeros cross every
-// feature slice in one wave instead of one wave per slice.  0 = off; -1 = the
-// rule (Ts = kShortWideTs on launches of at least kWideRowsMin rows); 1..32
-// forces Ts on every launch that can take them (the multi-row kernel at 32
-// lanes per row, a light order, at least two slices, no fused hub rows).  The
-// caller passes the count of light rows above Ts with Ts itself (the plan
-// counts them for 4 / 8 / 16 / 32), so the knob moves without re-planning;
-// "short_wide_ts" reports the Ts in force (0 = off).  Set through
-// sgc_set_tuning("short_wide").
-static int g_short_wide = -1;
-constexpr int kShortWideTs = 16;
-// the wide waves' workgroups before (1) or after (0) the slices' in the grid
-static int g_short_wide_first = 0;
+// The SpMM knobs (spmm_schedule.h describes each) and the knob table: one
+// row per sgc_set_tuning key -- where it lives, what it accepts, what a
+// rejected value is told.  get_tuning reads the same rows.
+static SpmmKnobs g_knobs;
 // launches that took wide items since the library was loaded (diagnostics)
 static std::atomic<int64_t> g_short_wide_launches{0};
 
-extern int g_x16_vec, g_x16_step;  // spmm16.hip
+namespace {
+struct Knob {
+    const char *name;
+    int *value;
+    bool (*ok)(int64_t);
+    const char *message;
+};
+template <int64_t... Vs>
+bool one_of(int64_t v) { return ((v == Vs) || ...); }
+template <int64_t Lo, int64_t Hi>
+bool within(int64_t v) { return v >= Lo && v <= Hi; }
+const Knob kKnobs[] = {
+    {"slice_floats", &g_knobs.slice_floats, within<0, (1 << 20) - 1>, "slice_floats out of range"},
+    {"hub_chunk", &g_knobs.hub_chunk, one_of<0, 32, 64>, "hub_chunk must be 0 (auto), 32 or 64"},
+    {"hub_loaders", &g_knobs.hub_loaders, one_of<7, 15>, "hub_loaders must be 7 or 15"},
+    {"hub_fuse", &g_knobs.hub_fuse, one_of<0, 1>, "hub_fuse must be 0 or 1"},
+    {"hub_stream", &g_knobs.hub_stream, within<0, 2>, "hub_stream must be 0, 1 or 2"},
+    {"rows_per_wave", &g_knobs.rows_per_wave, one_of<0, 1, 2, 4>,
+     "rows_per_wave must be 0 (auto), 1, 2 or 4"},
+    {"heavy_pairs", &g_knobs.heavy_pairs, within<0, 31>, "heavy_pairs must be 0..31 (a bit mask)"},
+    {"x16_vec", &g_x16_vec, one_of<0, 1, 2, 4, 8>, "x16_vec must be 0 (auto), 1, 2, 4 or 8"},
+    {"x16_step", &g_x16_step, one_of<0, 4, 8>, "x16_step must be 0 (auto), 4 or 8"},
+    {"tile_buffers", &g_tile_buffers, one_of<1, 2>, "tile_buffers must be 1 or 2"},
+    {"linear_ck", &g_linear_ck, one_of<32, 64>, "linear_ck must be 32 or 64"},
+    {"linear_kernel", &g_linear_kernel, within<0, 8>, "linear_kernel must be 0..8"},
+    {"backward_kernel", &g_backward_kernel, within<0, 3>, "backward_kernel must be 0..3"},
+    {"max_vec", &g_knobs.max_vec, one_of<1, 2, 4>, "max_vec must be 1, 2 or 4"},
+    {"short_wide", &g_knobs.short_wide, within<-1, 32>,
+     "short_wide must be -1 (the rule), 0 (off) or 1..32"},
+    {"short_wide_first", &g_knobs.short_wide_first, one_of<0, 1>, "short_wide_first must be 0 or 1"},
+};
+}  // namespace
 
 int set_tuning(const char *key, int64_t value) {
     SGC_REQUIRE(key, SGC_EINVAL, "set_tuning: null key");
-    if (std::string(key) == "slice_floats") {
-        SGC_REQUIRE(value >= 0 && value < (1 << 20), SGC_EINVAL, "slice_floats out of range");
-        g_slice_floats = (int)value;
-        return SGC_OK;
-    }
-    if (std::string(key) == "hub_chunk") {
-        SGC_REQUIRE(value == 0 || value == 32 || value == 64, SGC_EINVAL,
-                    "hub_chunk must be 0 (auto), 32 or 64");
-        g_hub_chunk = (int)value;
-        return SGC_OK;
-    }
-    if (std::string(key) == "hub_loaders") {
-        SGC_REQUIRE(value == 7 || value == 15, SGC_EINVAL, "hub_loaders must be 7 or 15");
-        g_hub_loaders = (int)value;
-        return SGC_OK;
-    }
-    if (std::string(key) == "hub_fuse") {
-        SGC_REQUIRE(value == 0 || value == 1, SGC_EINVAL, "hub_fuse must be 0 or 1");
-        g_hub_fuse = (int)value;
-        return SGC_OK;
-    }
-    if (std::string(key) == "hub_stream") {
-        SGC_REQUIRE(value >= 0 && value <= 2, SGC_EINVAL, "hub_stream must be 0, 1 or 2");
-        g_hub_stream = (int)value;
-        return SGC_OK;
-    }
-    if (std::string(key) == "rows_per_wave") {
-        SGC_REQUIRE(value == 0 || value == 1 || value == 2 || value == 4, SGC_EINVAL,
-                    "rows_per_wave must be 0 (auto), 1, 2 or 4");
-        g_rows_per_wave = (int)value;
-        return SGC_OK;
-    }
-    if (std::string(key) == "heavy_pairs") {
-        SGC_REQUIRE(value >= 0 && value <= 31, SGC_EINVAL, "heavy_pairs must be 0..31 (a bit mask)");
-        g_heavy_pairs = (int)value;
-        return SGC_OK;
-    }
-    if (std::string(key) == "x16_vec") {
-        SGC_REQUIRE(value == 0 || value == 1 || value == 2 || value == 4 || value == 8,
-                    SGC_EINVAL, "x16_vec must be 0 (auto), 1, 2, 4 or 8");
-        g_x16_vec = (int)value;
-        return SGC_OK;
-    }
-    if (std::string(key) == "x16_step") {
-        SGC_REQUIRE(value == 0 || value == 4 || value == 8, SGC_EINVAL,
-                    "x16_step must be 0 (auto), 4 or 8");
-        g_x16_step = (int)value;
-        return SGC_OK;
-    }
-    if (std::string(key) == "tile_buffers") {
-        SGC_REQUIRE(value == 1 || value == 2, SGC_EINVAL, "tile_buffers must be 1 or 2");
-        g_tile_buffers = (int)value;
-        return SGC_OK;
-    }
-    if (std::string(key) == "linear_ck") {
-        SGC_REQUIRE(value == 32 || value == 64, SGC_EINVAL, "linear_ck must be 32 or 64");
-        g_linear_ck = (int)value;
-        return SGC_OK;
-    }
-    if (std::string(key) == "linear_kernel") {
-        SGC_REQUIRE(value >= 0 && value <= 8, SGC_EINVAL, "linear_kernel must be 0..8");
-        g_linear_kernel = (int)value;
-        return SGC_OK;
-    }
-    if (std::string(key) == "backward_kernel") {
-        SGC_REQUIRE(value >= 0 && value <= 3, SGC_EINVAL, "backward_kernel must be 0..3");
-        g_backward_kernel = (int)value;
-        return SGC_OK;
-    }
-    if (std::string(key) == "max_vec") {
-        SGC_REQUIRE(value == 1 || value == 2 || value == 4, SGC_EINVAL, "max_vec must be 1, 2 or 4");
-        g_max_vec = (int)value;
-        return SGC_OK;
-    }
-    if (std::string(key) == "short_wide") {
-        SGC_REQUIRE(value >= -1 && value <= 32, SGC_EINVAL,
-                    "short_wide must be -1 (the rule), 0 (off) or 1..32");
-        g_short_wide = (int)value;
-        return SGC_OK;
-    }
-    if (std::string(key) == "short_wide_first") {
-        SGC_REQUIRE(value == 0 || value == 1, SGC_EINVAL, "short_wide_first must be 0 or 1");
-        g_short_wide_first = (int)value;
+    for (const Knob &k : kKnobs) {
+        if (std::strcmp(key, k.name) != 0) continue;
+        SGC_REQUIRE(k.ok(value), SGC_EINVAL, "%s", k.message);
+        *k.value = (int)value;
         return SGC_OK;
     }
     set_error("set_tuning: unknown key '%s'", key);
@@ -1686,94 +1497,126 @@ int set_tuning(const char *key, int64_t value) {
 }
 
 int64_t get_tuning(const char *key) {
+    if (!key) return -1;
+    const int sw = g_knobs.short_wide;
     // (first: the Python layer reads it once per propagate() call)
-    if (key && std::string(key) == "short_wide_state")
-        return (int64_t)(g_short_wide + 1) * 64 + (g_short_wide < 0 ? kShortWideTs : g_short_wide);
-    if (key && std::string(key) == "slice_floats") return g_slice_floats;
-    if (key && std::string(key) == "max_vec") return g_max_vec;
-    if (key && std::string(key) == "heavy_pairs") return g_heavy_pairs;
-    if (key && std::string(key) == "rows_per_wave") return g_rows_per_wave;
-    if (key && std::string(key) == "hub_chunk") return g_hub_chunk;
-    if (key && std::string(key) == "hub_stream") return g_hub_stream;
-    if (key && std::string(key) == "hub_loaders") return g_hub_loaders;
-    if (key && std::string(key) == "hub_fuse") return g_hub_fuse;
-    if (key && std::string(key) == "x16_vec") return g_x16_vec;
-    if (key && std::string(key) == "x16_step") return g_x16_step;
-    if (key && std::string(key) == "tile_buffers") return g_tile_buffers;
-    if (key && std::string(key) == "linear_kernel") return g_linear_kernel;
-    if (key && std::string(key) == "linear_ck") return g_linear_ck;
-    if (key && std::string(key) == "backward_kernel") return g_backward_kernel;
-    if (key && std::string(key) == "short_wide") return g_short_wide;
-    if (key && std::string(key) == "short_wide_ts")
-        return g_short_wide < 0 ? kShortWideTs : g_short_wide;
-    if (key && std::string(key) == "short_wide_first") return g_short_wide_first;
-    if (key && std::string(key) == "short_wide_launches") return g_short_wide_launches.load();
+    if (std::strcmp(key, "short_wide_state") == 0)
+        return (int64_t)(sw + 1) * 64 + (sw < 0 ? kShortWideTs : sw);
+    for (const Knob &k : kKnobs)
+        if (std::strcmp(key, k.name) == 0) return *k.value;
+    if (std::strcmp(key, "short_wide_ts") == 0) return sw < 0 ? kShortWideTs : sw;
+    if (std::strcmp(key, "short_wide_launches") == 0) return g_short_wide_launches.load();
     return -1;
 }
 
-int launch_spmm(const int32_t *row_ptr, const int32_t *col_idx, const float *val,
-                int64_t row_begin, int64_t row_end, const float *X, int64_t ldx, float *Y,
-                int64_t ldy, int64_t F, const int32_t *heavy_rows, int64_t n_heavy,
-                int64_t n_hub, int32_t heavy_threshold, uint32_t flags, hipStream_t stream,
-                int64_t n_nonempty, int64_t n_not_wide, int32_t wide_max_nnz) {
-    // col_idx / val may be NULL for a CSR without nonzeros (torch's empty
-    // tensors have no storage): the kernels never dereference them then
-    SGC_REQUIRE(row_ptr && X && Y, SGC_EINVAL, "spmm: null pointer");
-    SGC_REQUIRE(row_begin >= 0 && row_end >= row_begin && row_end < INT32_MAX, SGC_ERANGE,
-                "spmm: bad row range [%lld, %lld)", (long long)row_begin, (long long)row_end);
-    SGC_REQUIRE(F > 0 && F < (1 << 24), SGC_EINVAL, "spmm: bad feature count %lld", (long long)F);
-    SGC_REQUIRE(ldx >= F && ldy >= F, SGC_EINVAL, "spmm: ldx/ldy (%lld/%lld) < F (%lld)",
-                (long long)ldx, (long long)ldy, (long long)F);
-    SGC_REQUIRE(n_heavy >= 0 && (n_heavy == 0 || heavy_rows), SGC_EINVAL, "spmm: bad plan");
-    const int64_t n_rows = row_end - row_begin;
-    if (n_rows == 0) return SGC_OK;
-    // SGC_SPMM_LIGHT_ORDER: plan = [n_heavy heavy rows | the other rows in
-    // processing order] (taken before the hub split below moves heavy_rows)
-    const int *light_rows = nullptr;
-    int64_t n_light = 0;
-    if ((flags & SGC_SPMM_LIGHT_ORDER) && heavy_rows) {
-        SGC_REQUIRE(n_heavy <= n_rows, SGC_EINVAL, "spmm: light order with n_heavy > rows");
-        light_rows = heavy_rows + n_heavy;
-        n_light = n_rows - n_heavy;
+namespace {
+
+// The shape spmm_schedule looks at, from a call whose arguments passed
+// `validate` (the checks launch_spmm makes before anything else); *empty: a
+// launch over no rows, or SGC_SPMM_HUB_ONLY without hub rows -- nothing to do.
+int spmm_shape(const SpmmCall &c, bool validate, SpmmShape *sh, bool *empty) {
+    if (validate) {
+        // col_idx / val may be NULL for a CSR without nonzeros (torch's empty
+        // tensors have no storage): the kernels never dereference them then
+        SGC_REQUIRE(c.row_ptr && c.X && c.Y, SGC_EINVAL, "spmm: null pointer");
     }
-    // An accumulate launch leaves rows without nonzeros untouched, and the
-    // plan is sorted longest first: with the plan's count of rows that have
-    // nonzeros (n_nonempty >= 0; heavy rows are among them) the light items
-    // stop where the empty rows begin -- no wave is started for them (the
-    // multi-row kernel; the one-row kernel keeps row order over all rows,
-    // launch_vc).  A plain launch covers every row (an empty row is written
-    // as zeros).
-    if (light_rows && (flags & SGC_SPMM_ACCUMULATE) && n_nonempty >= 0) {
-        SGC_REQUIRE(n_nonempty >= n_heavy && n_nonempty <= n_rows, SGC_EINVAL,
-                    "spmm: n_nonempty %lld outside [n_heavy, rows]", (long long)n_nonempty);
-        n_light = n_nonempty - n_heavy;
+    SGC_REQUIRE(c.row_begin >= 0 && c.row_end >= c.row_begin && c.row_end < INT32_MAX, SGC_ERANGE,
+                "spmm: bad row range [%lld, %lld)", (long long)c.row_begin, (long long)c.row_end);
+    SGC_REQUIRE(c.F > 0 && c.F < (1 << 24), SGC_EINVAL, "spmm: bad feature count %lld",
+                (long long)c.F);
+    SGC_REQUIRE(c.ldx >= c.F && c.ldy >= c.F, SGC_EINVAL, "spmm: ldx/ldy (%lld/%lld) < F (%lld)",
+                (long long)c.ldx, (long long)c.ldy, (long long)c.F);
+    SGC_REQUIRE(c.n_heavy >= 0 && (c.n_heavy == 0 || c.plan), SGC_EINVAL, "spmm: bad plan");
+    sh->n_rows = c.row_end - c.row_begin;
+    *empty = sh->n_rows == 0;
+    if (*empty) return SGC_OK;
+    char err[160];
+    const int rc = spmm_plan_prologue("spmm", sh->n_rows, c.plan != nullptr, c.n_heavy, c.n_hub,
+                                      c.heavy_threshold, c.flags, c.n_nonempty, c.n_not_wide,
+                                      c.wide_max_nnz, g_knobs.short_wide, &sh->plan, err,
+                                      sizeof(err));
+    SGC_REQUIRE(rc == SGC_OK, rc, "%s", err);
+    *empty = (c.flags & SGC_SPMM_HUB_ONLY) && sh->plan.n_hub == 0;
+    sh->F = c.F;
+    sh->ldx = c.ldx;
+    sh->ldy = c.ldy;
+    sh->x_addr = reinterpret_cast<uintptr_t>(c.X);
+    sh->y_addr = reinterpret_cast<uintptr_t>(c.Y);
+    sh->flags = c.flags;
+    sh->wide_max_nnz = c.wide_max_nnz;
+    return SGC_OK;
+}
+
+hipError_t launch_hub(const LaunchArgs &a, const SpmmSchedule &s) {
+#define SGC_LAUNCH_HUB(HCV, NLV)                                                                \
+    hipLaunchKernelGGL((spmm_hub_kernel<HCV, NLV>), dim3((unsigned)s.hub_grid),                 \
+                       dim3(64 * (NLV + 1)), 0, a.stream, a.row_ptr, a.col, a.val, a.X, a.ldx,  \
+                       a.Y, a.ldy, a.row_begin, a.F, a.hub_rows, s.hub_n_chunks, a.accum)
+    if (s.hub_chunk == 32) {
+        if (s.hub_loaders == 7) SGC_LAUNCH_HUB(32, 7);
+        else SGC_LAUNCH_HUB(32, 15);
+    } else {
+        if (s.hub_loaders == 7) SGC_LAUNCH_HUB(64, 7);
+        else SGC_LAUNCH_HUB(64, 15);
     }
-    // Wide items: the caller's count of light rows with more than
-    // wide_max_nnz nonzeros (n_not_wide >= 0; the sorted plan lists them
-    // first) leaves the rest of the light items -- in a plain launch the
-    // rows without nonzeros too, written as zeros by the wide waves -- to
-    // wide waves, where the launch can take them (below).
-    int64_t n_wide = 0;
-    if (light_rows && n_not_wide >= 0 && g_short_wide != 0) {
-        SGC_REQUIRE(wide_max_nnz >= 1 && wide_max_nnz <= 32, SGC_EINVAL,
-                    "spmm: wide_max_nnz %d outside [1, 32]", wide_max_nnz);
-        SGC_REQUIRE(n_not_wide <= n_rows - n_heavy, SGC_EINVAL,
-                    "spmm: n_not_wide %lld > light rows", (long long)n_not_wide);
-        n_wide = std::max<int64_t>(0, n_light - n_not_wide);
+#undef SGC_LAUNCH_HUB
+    return hipGetLastError();
+}
+
+// The schedule's light kernel: one line per template instantiation.
+hipError_t launch_light(const LaunchArgs &a, const SpmmSchedule &s) {
+    if (s.grid_x == 0) return hipSuccess;  // an accumulate launch over empty runs
+    if (s.multi_row && s.WD) {
+#define SGC_WIDE(VHV, WDV)                                                  \
+    if (s.VH == VHV && s.WD == WDV)                                         \
+        return s.O32 ? launch_rows_wide<VHV, true, WDV>(a, s)               \
+                     : launch_rows_wide<VHV, false, WDV>(a, s)
+        SGC_WIDE(2, 16);
+        SGC_WIDE(1, 16);
+        SGC_WIDE(2, 32);
+        SGC_WIDE(1, 32);
+#undef SGC_WIDE
+    } else if (s.multi_row) {
+#define SGC_ROWS(LBV, VHV, QVV, HFV)                                        \
+    if (s.LB == LBV && s.VH == VHV && s.QV == QVV && s.HF == HFV)           \
+        return s.O32 ? launch_rows<LBV, VHV, true, QVV, HFV>(a, s)          \
+                     : launch_rows<LBV, VHV, false, QVV, HFV>(a, s)
+        SGC_ROWS(16, 2, 4, 0);
+        SGC_ROWS(8, 2, 4, 0);
+        SGC_ROWS(8, 2, 2, 0);
+        SGC_ROWS(8, 2, 1, 0);
+        SGC_ROWS(16, 2, 0, 32);
+        SGC_ROWS(16, 2, 0, 0);
+        SGC_ROWS(16, 1, 0, 0);
+        SGC_ROWS(8, 2, 0, 0);
+        SGC_ROWS(8, 1, 0, 0);
+#undef SGC_ROWS
+    } else if (s.HF) {
+        return launch_vc<4, 1, 32>(a, s);
+    } else if (s.V == 4) {
+        return dispatch_c<4, 16 / 4>(a, s);  // <= 16 accumulators per lane
+    } else if (s.V == 2) {
+        return dispatch_c<2, 16 / 2>(a, s);
+    } else {
+        return dispatch_c<1, 16 / 1>(a, s);
     }
-    if (!heavy_rows) {
-        n_heavy = 0;
-        heavy_threshold = INT32_MAX;  // no plan: every row is a light item
-    }
-    n_hub = std::max<int64_t>(0, std::min<int64_t>(n_hub, n_heavy));
-    if (flags & SGC_SPMM_NO_HUB) {  // hub rows are launched separately (SGC_SPMM_HUB_ONLY)
-        heavy_rows += n_hub;
-        n_heavy -= n_hub;
-        n_hub = 0;
-    }
-    const bool hub_only = (flags & SGC_SPMM_HUB_ONLY) != 0;
-    if (hub_only && n_hub == 0) return SGC_OK;
-    const int accum = (flags & SGC_SPMM_ACCUMULATE) ? 1 : 0;
+    return hipErrorInvalidValue;
+}
+
+}  // namespace
+
+// validate -> prologue -> spmm_schedule (spmm_schedule.h: every choice) ->
+// side stream and timing -> the schedule's launches.
+int launch_spmm(const SpmmCall &c, hipStream_t stream) {
+    SpmmShape sh;
+    bool empty = false;
+    int rc = spmm_shape(c, true, &sh, &empty);
+    if (rc != SGC_OK || empty) return rc;
+    SpmmSchedule s;
+    char err[160];
+    rc = spmm_schedule(sh, g_knobs, &s, err, sizeof(err));
+    SGC_REQUIRE(rc == SGC_OK, rc, "%s", err);
+
     SideStream *side = nullptr;
     std::unique_lock<std::mutex> side_lock;
     std::unique_lock<std::mutex> timing_lock(g_timing_mu);
@@ -1785,240 +1628,66 @@ int launch_spmm(const int32_t *row_ptr, const int32_t *col_idx, const float *val
     TimedGuard timed_guard;
     if (timing) timed_guard.tl = &tl;
     SideJoin side_join;
-    hipStream_t light_stream = stream;
-    // hub kernel launch (on the caller's stream) of the n_hub rows at hub_rows
-    const bool lines = ldx % 32 == 0 && reinterpret_cast<uintptr_t>(X) % 128 == 0;
-    const int32_t *hub_rows = heavy_rows;
-    auto launch_hub = [&](hipStream_t hs, int hc) -> hipError_t {
-        const int n_chunks = (int)((F + hc - 1) / hc);
-        const dim3 hub_grid((unsigned)(n_hub * n_chunks));
-#define SGC_LAUNCH_HUB(HCV, NLV)                                                             \
-    hipLaunchKernelGGL((spmm_hub_kernel<HCV, NLV>), hub_grid, dim3(64 * (NLV + 1)), 0, hs,   \
-                       row_ptr, col_idx, val, X, ldx, Y, ldy, (int)row_begin, (int)F,        \
-                       hub_rows, n_chunks, accum)
-        if (hc == 32) {
-            if (g_hub_loaders == 7) SGC_LAUNCH_HUB(32, 7);
-            else SGC_LAUNCH_HUB(32, 15);
-        } else {
-            if (g_hub_loaders == 7) SGC_LAUNCH_HUB(64, 7);
-            else SGC_LAUNCH_HUB(64, 15);
-        }
-#undef SGC_LAUNCH_HUB
-        return hipGetLastError();
-    };
-    // 32-feature chunks spread a hub over more CUs; measured faster up to
-    // F = 160 and slower from F = 320 (scripts/sweep_narrow.py), and they
-    // need 128-B aligned rows to stay one line per segment.
-    const int hub_hc = g_hub_chunk ? g_hub_chunk : (lines && F <= 192 ? 32 : 64);
-    bool hub_deferred = false;  // serial hub rows left for the fused launch (or just before the light kernel)
-    if (n_hub > 0) {
-        // hub rows (the heaviest n_hub of the plan) run beside the light
-        // kernel (g_hub_stream)
-        SGC_REQUIRE(n_hub * ((F + 31) / 32) < (int64_t)INT32_MAX, SGC_ERANGE,
-                    "spmm: too many hub items");
-        const hipStream_t hs = stream;  // always the caller's stream
-        const bool serial =
-            g_hub_stream == 2 || (g_hub_stream == 0 && (flags & SGC_SPMM_HUB_SERIAL));
-        // (the fused items read floats one at a time: any row alignment)
-        hub_deferred = serial && !hub_only && g_hub_fuse && g_hub_chunk == 0;
-        if (!hub_deferred) {
-            if (!hub_only && !serial) {
-                SGC_HIP_CHECK(side_stream(&side, stream));
-                side_lock = std::unique_lock<std::mutex>(side->mu);
-                SGC_HIP_CHECK(hipEventRecord(side->fork, stream));
-                SGC_HIP_CHECK(hipStreamWaitEvent(side->s, side->fork, 0));
-                side_join.side = side;  // from here on every exit joins
-                side_join.stream = stream;
-                light_stream = side->s;  // the hub kernel stays on the caller's stream
-                tl.hub_first = true;
-            }
-            if (timing) {
-                SGC_HIP_CHECK(pooled_event(&tl.h0));
-                SGC_HIP_CHECK(pooled_event(&tl.h1));
-                SGC_HIP_CHECK(hipEventRecord(tl.h0, hs));
-                tl.serial = hs == light_stream;
-            }
-            SGC_HIP_CHECK(launch_hub(hs, hub_hc));
-            if (timing) SGC_HIP_CHECK(hipEventRecord(tl.h1, hs));
-        }
-        heavy_rows += n_hub;
-        n_heavy -= n_hub;
-        if (hub_only) {
-            if (timing) {  // no light kernel: an empty light interval
-                SGC_HIP_CHECK(pooled_event(&tl.l0));
-                SGC_HIP_CHECK(pooled_event(&tl.l1));
-                SGC_HIP_CHECK(hipEventRecord(tl.l0, hs));
-                SGC_HIP_CHECK(hipEventRecord(tl.l1, hs));
-                timed_guard.commit();
-            }
-            return SGC_OK;
-        }
+    const int32_t *hub_rows = c.plan ? c.plan + sh.plan.heavy_skip : nullptr;
+    LaunchArgs a{c.row_ptr, c.col_idx, c.val, c.X, c.ldx, c.Y, c.ldy, (int)c.row_begin,
+                 (int)sh.n_rows, (int)c.F, hub_rows ? hub_rows + sh.plan.n_hub : nullptr,
+                 sh.plan.heavy_threshold, (c.flags & SGC_SPMM_ACCUMULATE) ? 1 : 0, stream,
+                 // (used by the multi-row kernel; the one-row kernel: natural order)
+                 sh.plan.light_offset >= 0 ? c.plan + sh.plan.light_offset : nullptr, hub_rows};
+    if (s.hub == kHubConcurrent) {
+        SGC_HIP_CHECK(side_stream(&side, stream));
+        side_lock = std::unique_lock<std::mutex>(side->mu);
+        SGC_HIP_CHECK(hipEventRecord(side->fork, stream));
+        SGC_HIP_CHECK(hipStreamWaitEvent(side->s, side->fork, 0));
+        side_join.side = side;  // from here on every exit joins
+        side_join.stream = stream;
+        tl.hub_first = true;
     }
-    // a deferred hub launch that the fused kernel does not take runs here,
-    // serially before the light kernel, as it would have
-    auto hub_before_light = [&]() -> int {
+    if (s.hub == kHubConcurrent || s.hub == kHubSerial) {
+        // the hub kernel: always on the caller's stream
         if (timing) {
             SGC_HIP_CHECK(pooled_event(&tl.h0));
             SGC_HIP_CHECK(pooled_event(&tl.h1));
             SGC_HIP_CHECK(hipEventRecord(tl.h0, stream));
-            tl.serial = true;
+            tl.serial = s.hub == kHubSerial;
         }
-        SGC_HIP_CHECK(launch_hub(stream, hub_hc));
+        SGC_HIP_CHECK(launch_hub(a, s));
         if (timing) SGC_HIP_CHECK(hipEventRecord(tl.h1, stream));
-        return SGC_OK;
-    };
-
-    LaunchArgs a{row_ptr, col_idx, val, X, ldx, Y, ldy, (int)row_begin, (int)n_rows, (int)F,
-                 heavy_rows, (int)n_heavy, heavy_threshold, 0, accum, light_stream};
-    a.light_rows = light_rows;  // used by the multi-row kernel (the one-row kernel: natural order)
-    a.n_light = (int)n_light;
-    // 16-B lanes over F rounded up to 4 columns: X rows must be 16-B aligned
-    // and readable that far (flag SGC_SPMM_X_PADDED unless F % 4 == 0)
-    const int64_t F4 = (F + 3) / 4 * 4;
-    const uintptr_t xa = reinterpret_cast<uintptr_t>(X), ya = reinterpret_cast<uintptr_t>(Y);
-    const bool v4_ok = ldx % 4 == 0 && xa % 16 == 0 && F4 <= ldx && F4 >= 32 &&
-                       (F4 == F || (flags & SGC_SPMM_X_PADDED));
-    // With both buffers padded, the one-row kernel may compute F rounded up
-    // to 4 as well: one 256-float slice (16-B lanes) covers a 129..256-float
-    // launch that the multi-row kernel would run as two passes (128 + the
-    // rest) -- e.g. a 146-column feature block at P = 4.  Wider launches keep
-    // the multi-row kernel's 128-float slices (Reddit's 602: MALL residency).
-    const bool pad_both = (flags & SGC_SPMM_X_PADDED) && (flags & SGC_SPMM_Y_PADDED);
-    const int64_t F_csr =
-        (F % 4 != 0 && pad_both && F4 > 128 && F4 <= 256 && F4 <= ldx && F4 <= ldy) ? F4 : F;
-    const bool csr_v4 = F_csr % 4 == 0 && pick_vec(F_csr, ldx, ldy, X, Y) == 4;
-    // Small, wide launches (Cora shape: 2,708 rows x 1,433 features, X in
-    // L2): latency-bound, so fewer and wider work items win -- the one-row
-    // kernel with 512-float slices, 19.7 vs 24.9 us per hop for the
-    // 128-float rows kernel (profiles/r02/small_shapes_sweep.log).  Only at
-    // the default schedule knobs.
-    const bool small_wide = n_rows * F <= (int64_t(1) << 23) && F > 256 &&
-                            g_rows_per_wave == 0 && g_slice_floats == 128;
-    const bool wide_rows = n_rows >= kWideRowsMin && (F4 == 128 || F4 > 256);
-    const bool rows_kernel = v4_ok && g_rows_per_wave != 1 && !small_wide &&
-                             (g_rows_per_wave > 1 || !csr_v4 || F4 < 128 || wide_rows);
-    hipError_t e = hipSuccess;
-    if (rows_kernel) {
-        const int vec_store = ldy % 4 == 0 && ya % 16 == 0 && F4 <= ldy &&
-                              (F4 == F || (flags & SGC_SPMM_Y_PADDED));
-        // lanes per row: the launch's width in 4-float lanes when it fits a
-        // wave's half or less (one slice), else 32 (or 16 when forced)
-        int LR = F4 >= 128 ? (g_rows_per_wave == 4 ? 16 : 32) : (int)(F4 / 4);
-        if (LR > 32) LR = 32;
-        const int SW = LR * 4;
-        const bool multi = F4 > SW;
-        const bool vh2 = F % 2 == 0 && ldx % 2 == 0 && ldy % 2 == 0 && xa % 8 == 0 &&
-                         ya % 8 == 0 && (!multi || SW % (kWave * 2) == 0);
-        SGC_REQUIRE(n_heavy * 8 + n_rows < (int64_t)INT32_MAX, SGC_ERANGE,
-                    "spmm: too many work items");
-        // the fused hub items need the 256-thread multi-row kernel with
-        // 16-B lanes over whole slices (LR >= 16, two-float heavy sub-chunks)
-        const bool fused = hub_deferred && LR >= 16 && vh2 && F4 > 64;
-        if (hub_deferred && !fused) {
-            const int rc = hub_before_light();
-            if (rc != SGC_OK) return rc;
-        }
-        if (fused) {
-            a.hub_rows = hub_rows;
-            a.hub_chunks = (int)((F + 31) / 32);
-            a.n_hub_blocks = (int)(n_hub * a.hub_chunks);
-        }
-        if (timing) {
-            SGC_HIP_CHECK(pooled_event(&tl.l0));
-            SGC_HIP_CHECK(pooled_event(&tl.l1));
-            SGC_HIP_CHECK(hipEventRecord(tl.l0, light_stream));
-            tl.kernel = fused ? 2 : 1;
-        }
-        // 32-bit row offsets (one full-rate 24-bit multiply per gathered row)
-        // when the caller vouches that X spans < 4 GiB and has < 2^24 rows
-        const bool o32 = (flags & SGC_SPMM_X_UNDER_4G) && ldx * 4 < (int64_t(1) << 24);
-#define SGC_ROWS(LBV, VHV, QVV)                                                     \
-    (o32 ? launch_rows<LBV, VHV, true, QVV>(a, (int)F4, LR, vec_store)              \
-         : launch_rows<LBV, VHV, false, QVV>(a, (int)F4, LR, vec_store))
-        // heavy rows four nonzeros per load (row_quads_pipe) on launches of at
-        // most 32 floats; measured (one hop over all Reddit-shape rows,
-        // interleaved, bit-identical, profiles/r04/quads_ab.log) 32 floats
-        // 0.667 -> 0.615 ms, but 48 and 64 floats slower (0.68 -> 0.82, 0.72
-        // -> 0.85) and 64-float slices at full width far slower (3.8 -> 5.8):
-        // there the pairs stay
-        int qv = ((g_heavy_pairs & 4) && LR <= 16 && F4 <= 32) ? (F4 > 16 ? 2 : 1) : 0;
-        // 33..64 floats: the transposed quads (row_quadsT_pipe, heavy_pairs bit 8)
-        if ((g_heavy_pairs & 8) && LR <= 16 && F4 > 32 && F4 <= 64) qv = 4;
-        // wide items: 32 lanes per row over at least two slices, no fused
-        // hub rows; the rule asks for a large launch, a forced Ts does not
-        const bool wide = n_wide > 0 && LR == 32 && multi && !fused && qv == 0 &&
-                          (g_short_wide > 0 || n_rows >= kWideRowsMin);
-        if (wide) {
-            a.n_wide = (int)n_wide;
-            a.wide_first = g_short_wide_first;
-            g_short_wide_launches.fetch_add(1, std::memory_order_relaxed);
-#define SGC_WIDE(WDV)                                                                       \
-    (vh2 ? (o32 ? launch_rows_wide<2, true, WDV>(a, (int)F4, vec_store)                     \
-                : launch_rows_wide<2, false, WDV>(a, (int)F4, vec_store))                   \
-         : (o32 ? launch_rows_wide<1, true, WDV>(a, (int)F4, vec_store)                     \
-                : launch_rows_wide<1, false, WDV>(a, (int)F4, vec_store)))
-            e = wide_max_nnz <= 16 ? SGC_WIDE(16) : SGC_WIDE(32);
-#undef SGC_WIDE
-        } else if (qv == 4)  // the light rows' LDS block: LB * rows per wave <= 64
-            e = LR >= 16 ? SGC_ROWS(16, 2, 4) : SGC_ROWS(8, 2, 4);
-        else if (qv == 2)
-            e = SGC_ROWS(8, 2, 2);
-        else if (qv == 1)
-            e = SGC_ROWS(8, 2, 1);
-        else if (fused)
-            e = o32 ? launch_rows<16, 2, true, 0, 32>(a, (int)F4, LR, vec_store)
-                    : launch_rows<16, 2, false, 0, 32>(a, (int)F4, LR, vec_store);
-        else if (LR >= 16)
-            e = vh2 ? SGC_ROWS(16, 2, 0) : SGC_ROWS(16, 1, 0);
-        else
-            e = vh2 ? SGC_ROWS(8, 2, 0) : SGC_ROWS(8, 1, 0);
-#undef SGC_ROWS
-    } else {
-        const int V = pick_vec(F_csr, ldx, ldy, X, Y);
-        a.F = (int)(V == 4 ? F_csr : F);  // pad columns only with 16-B lanes
-        const int chunks_total = (int)((a.F + kWave * V - 1) / (kWave * V));
-        const int cmax = max_chunks(V);
-        const int sf = small_wide ? 512 : g_slice_floats;
-        int C = sf > 0 ? std::max(1, sf / (kWave * V)) : cmax;
-        C = std::min(C, std::min(cmax, chunks_total));
-        const int slices = (chunks_total + C - 1) / C;
-        const int64_t waves = n_heavy * (int64_t)C * V + n_rows;  // upper bound (VH >= 1)
-        SGC_REQUIRE(waves < (int64_t)INT32_MAX, SGC_ERANGE, "spmm: too many work items");
-        SGC_REQUIRE(slices < 65536, SGC_ERANGE, "spmm: too many feature slices");
-        a.slices = slices;
-        // the fused hub items: the 16-B-lane, one-chunk slice form (Pubmed shape)
-        const bool fused = hub_deferred && V == 4 && C == 1;
-        if (hub_deferred && !fused) {
-            const int rc = hub_before_light();
-            if (rc != SGC_OK) return rc;
-        }
-        if (fused) {
-            a.hub_rows = hub_rows;
-            a.hub_chunks = (int)((F + 31) / 32);
-            a.n_hub_blocks = (int)(n_hub * a.hub_chunks);
-        }
-        if (timing) {
-            SGC_HIP_CHECK(pooled_event(&tl.l0));
-            SGC_HIP_CHECK(pooled_event(&tl.l1));
-            SGC_HIP_CHECK(hipEventRecord(tl.l0, light_stream));
-            tl.kernel = fused ? 3 : 0;
-        }
-        if (fused)
-            e = launch_vc<4, 1, 32>(a);
-        else if (V == 4)
-            e = dispatch_c<4, max_chunks(4)>(C, a);
-        else if (V == 2)
-            e = dispatch_c<2, max_chunks(2)>(C, a);
-        else
-            e = dispatch_c<1, max_chunks(1)>(C, a);
     }
-    SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "spmm launch failed: %s", hipGetErrorString(e));
+    if (side) a.stream = side->s;  // the light kernel beside the hub kernel
+    if (timing) {  // (SGC_SPMM_HUB_ONLY: no light kernel, an empty light interval)
+        SGC_HIP_CHECK(pooled_event(&tl.l0));
+        SGC_HIP_CHECK(pooled_event(&tl.l1));
+        SGC_HIP_CHECK(hipEventRecord(tl.l0, a.stream));
+        tl.kernel = s.kernel;
+    }
+    if (s.kernel >= 0) {
+        if (s.WD) g_short_wide_launches.fetch_add(1, std::memory_order_relaxed);
+        const hipError_t e = launch_light(a, s);
+        SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "spmm launch failed: %s", hipGetErrorString(e));
+    }
     if (timing) {
-        SGC_HIP_CHECK(hipEventRecord(tl.l1, light_stream));
+        SGC_HIP_CHECK(hipEventRecord(tl.l1, a.stream));
         timed_guard.commit();
     }
     if (side) SGC_HIP_CHECK(side_join.join());  // the caller's stream waits for the hub kernel
     return SGC_OK;
+}
+
+const char *spmm_kernel_name(const SpmmCall &c) {
+    static thread_local char name[256];
+    SpmmShape sh;
+    SpmmSchedule s;
+    bool empty = false;
+    char err[160];
+    if (spmm_shape(c, false, &sh, &empty) != SGC_OK) return "none";
+    if (empty) return "none";
+    if (spmm_schedule(sh, g_knobs, &s, err, sizeof(err)) != SGC_OK) {
+        set_error("%s", err);
+        return "none";
+    }
+    spmm_schedule_name(s, name, sizeof(name));
+    return name;
 }
 
 #if SGC_HUB_STAMPS
@@ -2102,7 +1771,8 @@ int launch_pad_rows(const float *src, int64_t lds, float *dst, int64_t ldd, int6
                 SGC_EINVAL, "pad_rows: bad arguments");
     if (n_rows == 0 || F == 0) return SGC_OK;
     const int64_t blocks = std::min<int64_t>((n_rows + 3) / 4, 256 * 16);
-    const int V = pick_vec(F, lds, ldd, src, dst);
+    const int V = spmm_pick_vec(g_knobs, F, lds, ldd, reinterpret_cast<uintptr_t>(src),
+                                reinterpret_cast<uintptr_t>(dst));
     if (V == 4)
         hipLaunchKernelGGL(pad_rows_kernel<4>, dim3(blocks), dim3(256), 0, stream, src, lds, dst,
                            ldd, n_rows, (int)F);

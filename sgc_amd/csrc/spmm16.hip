@@ -33,17 +33,13 @@
 // writable (SGC_SPMM_X_PADDED / SGC_SPMM_Y_PADDED: up to F rounded up to 8).
 #include "common.h"
 #include "hub.h"
+#include "internal.h"
+#include "spmm_schedule.h"
 #include "x16.h"
 
 #include <algorithm>
 
 namespace sgc {
-
-int64_t get_tuning(const char *key);
-// the hub launch's side stream (spmm.hip): fork the light kernel's stream off
-// `stream`, join it back (every fork is joined)
-int fork_light_stream(hipStream_t stream, hipStream_t *light, void **side);
-int join_light_stream(void *side, hipStream_t stream);
 
 // Schedule knobs (sgc_set_tuning; results never depend on them).
 // "x16_vec": the widest lane vector a launch may take, 8 / 4 / 2 / 1 elements
@@ -416,25 +412,18 @@ int launch_spmm_x16(const int32_t *row_ptr, const int32_t *col_idx, const float 
     SGC_REQUIRE(n_heavy >= 0 && (n_heavy == 0 || heavy_rows), SGC_EINVAL, "spmm_x16: bad plan");
     const int64_t n_rows = row_end - row_begin;
     if (n_rows == 0) return SGC_OK;
-    // SGC_SPMM_LIGHT_ORDER: plan = [n_heavy heavy rows | the other rows in
-    // processing order]
-    const int *light_rows = nullptr;
-    int64_t n_light = 0;
-    if ((flags & SGC_SPMM_LIGHT_ORDER) && heavy_rows) {
-        SGC_REQUIRE(n_heavy <= n_rows, SGC_EINVAL, "spmm_x16: light order with n_heavy > rows");
-        light_rows = heavy_rows + n_heavy;
-        n_light = n_rows - n_heavy;
-    }
-    if (!heavy_rows) {
-        n_heavy = 0;
-        heavy_threshold = INT32_MAX;  // no plan: every row is a light item
-    }
-    n_hub = std::max<int64_t>(0, std::min<int64_t>(n_hub, n_heavy));
-    if (flags & SGC_SPMM_NO_HUB) {  // hub rows are launched separately (SGC_SPMM_HUB_ONLY)
-        heavy_rows += n_hub;
-        n_heavy -= n_hub;
-        n_hub = 0;
-    }
+    // the plan prologue shared with launch_spmm (no non-empty or wide counts here)
+    SpmmPlan pl;
+    char err[160];
+    const int rc = spmm_plan_prologue("spmm_x16", n_rows, heavy_rows != nullptr, n_heavy, n_hub,
+                                      heavy_threshold, flags, -1, -1, 0, 0, &pl, err, sizeof(err));
+    SGC_REQUIRE(rc == SGC_OK, rc, "%s", err);
+    const int *light_rows = pl.light_offset >= 0 ? heavy_rows + pl.light_offset : nullptr;
+    const int64_t n_light = pl.n_light;
+    if (heavy_rows) heavy_rows += pl.heavy_skip;
+    n_heavy = pl.n_heavy;
+    n_hub = pl.n_hub;
+    heavy_threshold = pl.heavy_threshold;
     if ((flags & SGC_SPMM_HUB_ONLY) && n_hub == 0) return SGC_OK;
     SGC_REQUIRE(n_heavy * 2 + n_rows < (int64_t)INT32_MAX, SGC_ERANGE,
                 "spmm_x16: too many work items");

@@ -18,6 +18,7 @@
 //        (old column order); when idx is not ascending the new column ids of a
 //        row are not either, and a segmented radix sort by column fixes that.
 #include "common.h"
+#include "internal.h"
 
 #include <hipcub/hipcub.hpp>
 

@@ -37,6 +37,7 @@
 #ifndef SGC_XENT_STOP_PASS
 #include "adam_update.h"
 #include "gemm_tile.h"
+#include "internal.h"
 #include "split_bf16.h"
 
 #define SGC_XENT_KERNEL(name) name##_kernel
@@ -44,12 +45,6 @@
 #define SGC_XENT_STOP_TEST
 
 namespace sgc {
-
-// launch A behind the stop word: xent_fwd_stop_kernel<V, NT, g_tile_buffers> (xent_fwd_stop.hip)
-hipError_t launch_xent_fwd_stop(int V, int NT, const int64_t *stop, const float *X, int64_t ldx,
-                                const float *W, const float *b, const int64_t *labels, int M, int K,
-                                int C, float *G, int ldg, double *loss_part, float *db_part,
-                                float *logits, int64_t ldl, hipStream_t s);
 
 namespace {
 

@@ -5,6 +5,7 @@
 // wave-uniform load at entry returns when the word is set.  It is a unit of
 // its own so that xent.hip's code object holds the plain kernels alone.
 #include "gemm_tile.h"
+#include "internal.h"
 
 #define SGC_XENT_KERNEL(name) name##_stop_kernel
 #define SGC_XENT_STOP_PARAM const int64_t *__restrict__ stop,

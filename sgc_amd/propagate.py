@@ -878,16 +878,22 @@ def spmm(csr: DeviceCSR, X: torch.Tensor, row_begin=0, row_end=None, out=None,
         stream = _lib.stream_handle(X.device)
         for g, c in enumerate(parts):  # group 0 plain, groups 1.. continue its chains
             pl = c.plan(row_begin, row_end, threshold, hub_threshold, F) if use_plan else NO_PLAN
-            _lib.check(lib.sgc_spmm_csr_f32_ex3(_lib.ptr(c.row_ptr), _lib.ptr(c.col_idx),
-                                                _lib.ptr(c.val), row_begin, row_end, _lib.ptr(X),
-                                                X.stride(0), _lib.ptr(out), out.stride(0), F,
-                                                _lib.ptr(pl.rows), pl.n_heavy, pl.n_hub,
-                                                pl.threshold,
-                                                int(flags) | pl.hub_flags() | x_flags(X) |
-                                                (SPMM_ACCUMULATE if g else 0), pl.n_nonempty,
-                                                *wide_args(c, pl, row_begin, row_end),
-                                                stream), "spmm_csr_f32")
+            args = spmm_args(c, pl, row_begin, row_end, X, out,
+                             int(flags) | pl.hub_flags() | x_flags(X) |
+                             (SPMM_ACCUMULATE if g else 0), wide_args(c, pl, row_begin, row_end))
+            _lib.check(lib.sgc_spmm_csr_f32_ex3(*args, stream), "spmm_csr_f32")
     return out
+
+
+def spmm_args(csr, pl, row_begin, row_end, X, out, flags, wide):
+    """The arguments of sgc_spmm_csr_f32_ex3 before its stream (and of
+    sgc_launch_list_add_spmm_ex3 between its handle and its slots): CSR `csr`
+    with plan `pl` over rows [row_begin, row_end), X -> out, `wide` =
+    wide_args()'s (n_not_wide, wide_max_nnz)."""
+    return (_lib.ptr(csr.row_ptr), _lib.ptr(csr.col_idx), _lib.ptr(csr.val), int(row_begin),
+            int(row_end), _lib.ptr(X), X.stride(0), _lib.ptr(out), out.stride(0), X.shape[1],
+            _lib.ptr(pl.rows), pl.n_heavy, pl.n_hub, pl.threshold, int(flags), pl.n_nonempty,
+            *wide)
 
 
 class SpmmLaunch:
@@ -914,11 +920,9 @@ class SpmmLaunch:
         lib = _lib.load()
         self._fn = lib.sgc_spmm_csr_f32_ex3
         self._keep = (csr, X, out, pl) if keep_tensors else (csr, pl)
-        self._args = (_lib.ptr(csr.row_ptr), _lib.ptr(csr.col_idx), _lib.ptr(csr.val),
-                      int(row_begin), int(row_end), _lib.ptr(X), X.stride(0), _lib.ptr(out),
-                      out.stride(0), F, _lib.ptr(pl.rows), pl.n_heavy, pl.n_hub, pl.threshold,
-                      int(flags) | pl.hub_flags() | x_flags(X), pl.n_nonempty,
-                      *wide_args(csr, pl, int(row_begin), int(row_end)))
+        self._args = spmm_args(csr, pl, row_begin, row_end, X, out,
+                               int(flags) | pl.hub_flags() | x_flags(X),
+                               wide_args(csr, pl, int(row_begin), int(row_end)))
 
     def __call__(self, stream_handle):
         rc = self._fn(*self._args, stream_handle)
@@ -1079,10 +1083,7 @@ def propagate(csr: DeviceCSR, X: torch.Tensor, K: int, out=None, use_plan=True, 
             if hop_hook:
                 hop_hook("start", h)
             for (c, cp, gflags), w in zip(parts, wide):  # column groups: 0 plain, 1.. accumulate
-                args = (_lib.ptr(c.row_ptr), _lib.ptr(c.col_idx), _lib.ptr(c.val), 0, n,
-                        _lib.ptr(src), src.stride(0), _lib.ptr(dst), dst.stride(0), F,
-                        _lib.ptr(cp.rows), cp.n_heavy, cp.n_hub, cp.threshold, flags | gflags,
-                        cp.n_nonempty, *w)
+                args = spmm_args(c, cp, 0, n, src, dst, flags | gflags, w)
                 ops.append(("spmm", args, slot(src), slot(dst)))
                 _lib.check(lib.sgc_spmm_csr_f32_ex3(*args, stream), "spmm_csr_f32")
             if hop_hook:

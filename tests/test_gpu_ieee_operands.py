@@ -14,9 +14,11 @@ Rule (ieee_operands.compare): NaN exactly where the reference has NaN, payload
 and sign free; every other element bit-equal.  Reference: the oracle, which
 tests/test_ieee_operands_cpu.py shows equal to torch.spmm on these operands.
 
-Which kernel body a case reaches is argued from launch_spmm's dispatch
-(csrc/spmm.hip), not observed: there is no kernel-name query for the SpMM
-(only the wide items count their launches, and that counter is asserted).
+Which kernel body a case reaches is the choice of spmm_schedule()
+(csrc/spmm_schedule.h), which launch_spmm launches as returned:
+tests/test_spmm_schedule_host.py asks sgc_spmm_kernel_name for these
+parametrisations and asserts the bodies the docstrings below name (and the
+wide items count their launches; that counter is asserted here).
 Every knob is restored in `finally`.
 """
 import functools
@@ -178,11 +180,14 @@ ONE_HOP = [(F, how, rpw) for F in WIDTHS for how in ("lines", "contig", "slice")
 def test_one_hop_every_schedule(F, how, rows_per_wave):
     """spmm() under the six schedules.  Light rows: without 16-B lanes (F4 < 32,
     "slice", "contig" at F % 4 != 0) spmm_csr_kernel's row_chunks_pipe with 1-
-    or 2-float lanes, where rows_per_wave changes nothing and only 0 runs;
+    or 2-float lanes (4-float at 12 floats in aligned rows: the one-row kernel's
+    own lanes), where rows_per_wave changes nothing and only 0 runs;
     with them spmm_rows_kernel's LDS blocks (rows_per_wave 2 / 4, or 0 below
-    128 floats and at F % 4 != 0: 9..32 lanes per row, 1..5 slices) or the
-    one-row kernel with 16-B lanes (rows_per_wave 1; 0 at 130 / 152 / 256 and,
-    as the small-wide rule's 512-float slices, at 602).  Heavy rows (threshold
+    128 floats and at F % 4 != 0: 9..32 lanes per row, 1..5 slices, 10 at 602
+    floats and 16 lanes) or the one-row kernel (rows_per_wave 1: 16-B lanes at
+    F % 4 == 0 and at 130 padded floats, else 1- or 2-float lanes; 0: 16-B
+    lanes at 130 / 152 / 256 and, as the small-wide rule's 512-float slices of
+    2-float lanes, at 602).  Heavy rows (threshold
     0 / 16 / 40): row_pairs_pipe, row_quadsT_pipe at 33..64 floats, row_chunks_pipe
     sub-chunks.  Hub rows (0 / 200 / 500 and the default plan's 3001-nonzero
     rows): hub_body with hub_chain_dpp rounds and the scalar tail, fused into
