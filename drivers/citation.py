@@ -15,7 +15,10 @@ loaded features once: the propagated features, the training rows and the
 evaluation rows stay in that type, the weights and logits in float32.
 --device-adam (also this driver's own) trains with sgc_amd.optim.Adam's
 run_epochs: the same loop, enqueued on the GPU by one host call; without it
-the loop below runs through torch.optim.Adam as before.
+the loop below runs through torch.optim.Adam as before.  The two combine:
+--feature-dtype bfloat16 --device-adam trains on the 16-bit rows in one host
+call too (sgc_train_adam_x16; an odd feature count such as Cora's 1433 costs
+one even-pitch copy of the training rows per call).
 """
 import argparse
 import os
@@ -67,13 +70,21 @@ def test_regression(model, test_features, test_labels):
     return accuracy(model(test_features), test_labels)
 
 
+def parse_own(argv=None):
+    """This driver's own flags (the rest are get_citation_args')."""
+    own = argparse.ArgumentParser(add_help=False)
+    own.add_argument("--feature-dtype", choices=sorted(FEATURE_DTYPES), default="float32",
+                     help="storage type of the features; with --device-adam the 16-bit rows "
+                          "train in one host call as well")
+    own.add_argument("--device-adam", action="store_true", default=False,
+                     help="train with sgc_amd.optim.Adam.run_epochs (the epochs in one host call, "
+                          "on float32, bfloat16 or float16 features)")
+    return own.parse_known_args(argv)[0]
+
+
 def main(argv=None):
     args = get_citation_args(argv)
-    own = argparse.ArgumentParser(add_help=False)
-    own.add_argument("--feature-dtype", choices=sorted(FEATURE_DTYPES), default="float32")
-    own.add_argument("--device-adam", action="store_true", default=False,
-                     help="train with sgc_amd.optim.Adam.run_epochs (the epochs in one host call)")
-    own_args = own.parse_known_args(argv)[0]
+    own_args = parse_own(argv)
     feature_dtype = FEATURE_DTYPES[own_args.feature_dtype]
     if args.tuned:
         if args.model != "SGC":

@@ -3,6 +3,7 @@ reddit.py (same flags and output line), reading data/reddit_adj.npz and
 data/reddit.npz like the reference.
 
     python drivers/reddit.py [--inductive] [--test] [--degree 2] [--epochs 2]
+                             [--feature-dtype {float32,bfloat16,float16}] [--fused-lbfgs]
 
 Flow (reference reddit.py:12-74): seed -> load_reddit_data (A + A^T, train
 subgraph, AugNorm, standardised features) -> SGC(602, 41) -> sgc_precompute
@@ -51,10 +52,12 @@ def parse(argv=None):
     p.add_argument("--device-lbfgs", action="store_true", default=False,
                    help="train with sgc_amd.optim.LBFGS (no host synchronisation per iteration)")
     p.add_argument("--fused-lbfgs", action="store_true", default=False,
-                   help="train with sgc_amd.optim.LBFGS.run_steps (all steps in one host call)")
+                   help="train with sgc_amd.optim.LBFGS.run_steps (all steps in one host call, on "
+                        "float32, bfloat16 or float16 features)")
     p.add_argument("--feature-dtype", choices=sorted(FEATURE_DTYPES), default="float32",
                    help="storage type of the features: cast once after loading; the propagated "
-                        "features, the training and the evaluation rows stay in it")
+                        "features, the training and the evaluation rows stay in it (with "
+                        "--fused-lbfgs the 16-bit rows train in one host call as well)")
     args = p.parse_args(argv)
     args.cuda = not args.no_cuda and torch.cuda.is_available()
     return args

@@ -849,6 +849,79 @@ int sgc_train_adam_f32(const float *X, int64_t ldx, float *W, float *b, const in
                        void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Fused training on 16-bit features: the step, the Adam epochs and the L-BFGS
+ * steps above with X as torch.bfloat16 / torch.float16 rows (x_dtype
+ * SGC_DTYPE_BF16 / SGC_DTYPE_F16, ldx in 16-bit ELEMENTS); W, b, the loss,
+ * dW, db, the moments and the L-BFGS state stay fp32 and are the ones the
+ * _f32 entries use.  Each call has its _f32 counterpart's argument list with
+ * `const void *X, int32_t x_dtype` in place of `const float *X`; there is no
+ * logits output (sgc_linear_x16 gives the logits).
+ *
+ *   sgc_linear_xent_x16: three launches, X read twice at 16 bits:
+ *     A  logits float(x) . W^T + b by sgc_linear_x16's split-bf16 stream (one
+ *        piece for bf16: 3 MFMAs per class tile; two for fp16: 5), each
+ *        16-row tile followed at once by sgc_linear_xent_f32's row epilogue
+ *        (same formulas): G = (softmax - onehot) / M to the workspace and ONE
+ *        LOSS PARTIAL PER 16-ROW TILE, a double indexed by tile number (the
+ *        waves take tiles dynamically, so a per-wave partial would differ run
+ *        to run);
+ *     B  sgc_linear_backward_x16's kernel on G: dW partials over column
+ *        blocks x row ranges, db partials from the same G loads;
+ *     C  one launch that reduces dW, db and the loss, each in a fixed order.
+ *   sgc_train_adam_x16: sgc_train_adam_f32's general schedule -- per epoch A,
+ *     B and C with the Adam update applied in place by the thread that holds
+ *     the finished gradient element.  The small schedule is fp32-only: 16-bit
+ *     X runs the general one under every "adam_kernel" setting, and
+ *     "adam_kernel_last" reads 1 after such a call.
+ *   sgc_train_lbfgs_x16: sgc_train_lbfgs_f32's loop with the closure A, B, C
+ *     behind the state's stop word (every launch tests it with one
+ *     wave-uniform load at entry and returns when it is set).  The state is
+ *     sgc_lbfgs_init's; fused and stepwise steps may alternate on it.  The
+ *     result -- W, b, the whole state, every status and every loss -- is
+ *     bit-identical to the same steps driven closure by closure through
+ *     sgc_linear_xent_x16 and sgc_lbfgs_iterate_f32.
+ *
+ * Coverage: sgc_linear_xent_x16_kernel_name is the one authority (host only,
+ * dereferences nothing, "none" outside coverage).  It covers exactly the
+ * arguments for which sgc_linear_x16_kernel_name and
+ * sgc_linear_backward_x16_kernel_name both name a kernel: bf16 or fp16, even
+ * ldx >= K, X 4-B aligned, M * ldx * 2 < 2^31, W's operand image within LDS
+ * (launch A needs what sgc_linear_x16 needs: no further margin), C <= 48.
+ * sgc_train_lbfgs_x16 further needs C * K + C <= 65,536 (the L-BFGS state).
+ * Outside coverage -- an unknown dtype and an odd ldx included -- the calls
+ * return SGC_EINVAL with an sgc_last_error text before any pointer is touched,
+ * and there is no fp32 kernel behind these entry points.  The workspace
+ * functions return 0 where no layout of (M, K, C) is covered.  epochs == 0 /
+ * steps == 0 with valid arguments return SGC_OK and enqueue nothing.
+ *
+ * Contracts, as the fp32 entries': no host synchronisation, no allocation, no
+ * atomics on global memory; every sum in a fixed order, results bitwise
+ * reproducible run to run; results defined on the exactly widened elements
+ * (tolerance-equal to torch on X.float()); a non-finite x follows the
+ * deviation documented for sgc_linear_x16.  Labels must lie in [0, C).
+ * ------------------------------------------------------------------------- */
+int64_t sgc_linear_xent_x16_workspace(int64_t M, int64_t K, int64_t C);
+int sgc_linear_xent_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *W, const float *b,
+                        const int64_t *labels, int64_t M, int64_t K, int64_t C, float *loss,
+                        float *dW, float *db, void *ws, int64_t ws_bytes, void *stream);
+const char *sgc_linear_xent_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,
+                                            const void *X, int32_t x_dtype);
+int64_t sgc_train_adam_x16_workspace(int64_t M, int64_t K, int64_t C);
+int sgc_train_adam_x16(const void *X, int32_t x_dtype, int64_t ldx, float *W, float *b,
+                       const int64_t *labels, int64_t M, int64_t K, int64_t C,
+                       float *exp_avg_W, float *exp_avg_sq_W, float *exp_avg_b, float *exp_avg_sq_b,
+                       int64_t step0, int32_t epochs, double lr, double beta1, double beta2,
+                       double eps, double weight_decay, float *loss_trace,
+                       void *workspace, int64_t workspace_bytes, void *stream);
+int64_t sgc_train_lbfgs_x16_workspace(int64_t M, int64_t K, int64_t C);
+int sgc_train_lbfgs_x16(const void *X, int32_t x_dtype, int64_t ldx, float *W, float *b,
+                        const int64_t *labels, int64_t M, int64_t K, int64_t C, void *state,
+                        int32_t steps, double lr, int32_t max_iter, int32_t max_eval,
+                        double tolerance_grad, double tolerance_change, float *loss_trace,
+                        int64_t *status_trace, void *workspace, int64_t workspace_bytes,
+                        void *stream);
+
+/* ---------------------------------------------------------------------------
  * Host (CPU) twins, for CPU tensors: the reference runs utils.py:92-97 on the
  * CPU whenever CUDA is off (args.py:39 --no-cuda; load_citation(cuda=False)).
  * Every pointer here is a HOST pointer; the calls are synchronous and

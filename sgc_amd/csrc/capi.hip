@@ -653,6 +653,52 @@ int sgc_train_adam_f32(const float *X, int64_t ldx, float *W, float *b, const in
                       workspace, workspace_bytes, as_stream(stream));
 }
 
+int64_t sgc_linear_xent_x16_workspace(int64_t M, int64_t K, int64_t C) {
+    return linear_xent_x16_workspace_bytes(M, K, C);
+}
+
+int sgc_linear_xent_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *W, const float *b,
+                        const int64_t *labels, int64_t M, int64_t K, int64_t C, float *loss,
+                        float *dW, float *db, void *ws, int64_t ws_bytes, void *stream) {
+    return linear_xent_x16(X, x_dtype, ldx, W, b, labels, M, K, C, loss, dW, db, ws, ws_bytes,
+                           as_stream(stream));
+}
+
+const char *sgc_linear_xent_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,
+                                            const void *X, int32_t x_dtype) {
+    return linear_xent_x16_kernel_name(M, K, ldx, C, X, x_dtype);
+}
+
+int64_t sgc_train_adam_x16_workspace(int64_t M, int64_t K, int64_t C) {
+    return train_adam_x16_workspace(M, K, C);
+}
+
+int sgc_train_adam_x16(const void *X, int32_t x_dtype, int64_t ldx, float *W, float *b,
+                       const int64_t *labels, int64_t M, int64_t K, int64_t C, float *exp_avg_W,
+                       float *exp_avg_sq_W, float *exp_avg_b, float *exp_avg_sq_b, int64_t step0,
+                       int32_t epochs, double lr, double beta1, double beta2, double eps,
+                       double weight_decay, float *loss_trace, void *workspace,
+                       int64_t workspace_bytes, void *stream) {
+    return train_adam_x16(X, x_dtype, ldx, W, b, labels, M, K, C, exp_avg_W, exp_avg_sq_W,
+                          exp_avg_b, exp_avg_sq_b, step0, epochs, lr, beta1, beta2, eps,
+                          weight_decay, loss_trace, workspace, workspace_bytes, as_stream(stream));
+}
+
+int64_t sgc_train_lbfgs_x16_workspace(int64_t M, int64_t K, int64_t C) {
+    return train_lbfgs_x16_workspace(M, K, C);
+}
+
+int sgc_train_lbfgs_x16(const void *X, int32_t x_dtype, int64_t ldx, float *W, float *b,
+                        const int64_t *labels, int64_t M, int64_t K, int64_t C, void *state,
+                        int32_t steps, double lr, int32_t max_iter, int32_t max_eval,
+                        double tolerance_grad, double tolerance_change, float *loss_trace,
+                        int64_t *status_trace, void *workspace, int64_t workspace_bytes,
+                        void *stream) {
+    return train_lbfgs_x16(X, x_dtype, ldx, W, b, labels, M, K, C, state, steps, lr, max_iter,
+                           max_eval, tolerance_grad, tolerance_change, loss_trace, status_trace,
+                           workspace, workspace_bytes, as_stream(stream));
+}
+
 int sgc_warmup(uint32_t units, void *stream) {
     SGC_REQUIRE((units & ~7u) == 0, SGC_EINVAL, "warmup: unknown unit bits 0x%x", units);
     hipStream_t s = as_stream(stream);

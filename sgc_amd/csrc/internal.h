@@ -206,6 +206,34 @@ int64_t linear_backward_x16_workspace_bytes(int64_t M, int64_t K, int64_t C);
 int linear_backward_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *dY, int64_t ldd,
                         int64_t M, int64_t K, int64_t C, float *dW, float *db, void *ws,
                         int64_t ws_bytes, hipStream_t s);
+// linear16.hip: launch B of the fused 16-bit step (the plain kernel) and its row ranges
+int dw_cols_x16_ranges(int64_t M);
+hipError_t launch_dw_cols_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *G, int ldg,
+                              int M, int K, int C, float *slab, float *db_slab, hipStream_t s);
+// xent16.hip: the fused step and the training loops on 16-bit features
+const char *linear_xent_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,
+                                        const void *X, int32_t x_dtype);
+int64_t linear_xent_x16_workspace_bytes(int64_t M, int64_t K, int64_t C);
+int linear_xent_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *W, const float *b,
+                    const int64_t *labels, int64_t M, int64_t K, int64_t C, float *loss, float *dW,
+                    float *db, void *ws, int64_t ws_bytes, hipStream_t s);
+int xent_x16_closure_check(const char *what, const void *X, int32_t x_dtype, int64_t ldx, int64_t M,
+                           int64_t K, int64_t C);
+int xent_x16_closure(const int64_t *stop, const void *X, int32_t x_dtype, int64_t ldx,
+                     const float *W, const float *b, const int64_t *labels, int64_t M, int64_t K,
+                     int64_t C, float *loss, float *dW, float *db, void *ws, hipStream_t s);
+int64_t train_adam_x16_workspace(int64_t M, int64_t K, int64_t C);
+int train_adam_x16(const void *X, int32_t x_dtype, int64_t ldx, float *W, float *b,
+                   const int64_t *labels, int64_t M, int64_t K, int64_t C, float *mW, float *vW,
+                   float *mb, float *vb, int64_t step0, int32_t epochs, double lr, double beta1,
+                   double beta2, double eps, double weight_decay, float *loss_trace, void *ws,
+                   int64_t ws_bytes, hipStream_t s);
+int64_t train_lbfgs_x16_workspace(int64_t M, int64_t K, int64_t C);
+int train_lbfgs_x16(const void *X, int32_t x_dtype, int64_t ldx, float *W, float *b,
+                    const int64_t *labels, int64_t M, int64_t K, int64_t C, void *state,
+                    int32_t steps, double lr, int32_t max_iter, int32_t max_eval, double tol_grad,
+                    double tol_change, float *loss_trace, int64_t *status_trace, void *ws,
+                    int64_t ws_bytes, hipStream_t s);
 int64_t plan_sorted_workspace(int64_t n_rows);
 int64_t colsplit_workspace(int64_t n_rows, int32_t groups);
 int mgpu_init(int ndev, const int *devices);

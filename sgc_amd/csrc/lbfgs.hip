@@ -578,33 +578,22 @@ int64_t train_lbfgs_workspace(int64_t M, int64_t K, int64_t C) {
     return 256 + round_up((C * K + C) * 4, 256) + 256 + xent_workspace_bytes(M, K, C);
 }
 
-int train_lbfgs(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels, int64_t M,
-                int64_t K, int64_t C, void *state, int32_t steps, double lr, int32_t max_iter,
-                int32_t max_eval, double tol_grad, double tol_change, float *loss_trace,
-                int64_t *status_trace, void *ws, int64_t ws_bytes, hipStream_t s) {
-    SGC_REQUIRE(steps >= 0, SGC_EINVAL, "train_lbfgs: steps=%d < 0", steps);
-    SGC_REQUIRE(M > 0 && K > 0 && C > 0 && C <= 64 && ldx >= K, SGC_EINVAL,
-                "train_lbfgs: bad shape M=%lld K=%lld C=%lld ldx=%lld (1 <= C <= 64, ldx >= K)",
-                (long long)M, (long long)K, (long long)C, (long long)ldx);
-    SGC_REQUIRE(max_iter >= 1, SGC_EINVAL, "train_lbfgs: max_iter=%d < 1", max_iter);
-    SGC_REQUIRE(X && W && labels && state && ws, SGC_EINVAL, "train_lbfgs: null pointer");
-    SGC_REQUIRE(reinterpret_cast<uintptr_t>(X) % 4 == 0, SGC_EINVAL,
-                "train_lbfgs: X not 4-B aligned");
+// The steps' launches, shared by the fp32 and the 16-bit entry (arguments
+// checked by the caller): closure(stop, loss, dW, db, xent_ws) enqueues one
+// closure behind the stop word.
+template <typename Closure>
+static int run_train_steps(const char *what, Closure &&closure, float *W, float *b, int64_t K,
+                           int64_t C, void *state, int32_t steps, double lr, int32_t max_iter,
+                           int32_t max_eval, double tol_grad, double tol_change, float *loss_trace,
+                           int64_t *status_trace, void *ws, hipStream_t s) {
     const int64_t ck = C * K, n = ck + (b ? C : 0);
-    SGC_REQUIRE(n <= kMaxN, SGC_ERANGE, "train_lbfgs: n=%lld > %lld parameters", (long long)n,
-                (long long)kMaxN);
-    if (const int rc = xent_closure_check("train_lbfgs", M, K, C, ldx)) return rc;
-    const int64_t need = train_lbfgs_workspace(M, K, C);
-    SGC_REQUIRE(ws_bytes >= need, SGC_ENOMEM, "train_lbfgs: workspace %lld < %lld",
-                (long long)ws_bytes, (long long)need);
-    if (steps == 0) return SGC_OK;
     {
         std::lock_guard<std::mutex> lock(g_states_mu);
         auto it = g_states.find(state);
-        SGC_REQUIRE(it != g_states.end(), SGC_EINVAL,
-                    "train_lbfgs: state not initialised by sgc_lbfgs_init");
+        SGC_REQUIRE(it != g_states.end(), SGC_EINVAL, "%s: state not initialised by sgc_lbfgs_init",
+                    what);
         SGC_REQUIRE(it->second.n == n, SGC_EINVAL,
-                    "train_lbfgs: C*K%s = %lld parameters, the state was initialised for n=%lld",
+                    "%s: C*K%s = %lld parameters, the state was initialised for n=%lld", what,
                     b ? " + C" : "", (long long)n, (long long)it->second.n);
     }
     char *p = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
@@ -638,12 +627,11 @@ int train_lbfgs(const float *X, int64_t ldx, float *W, float *b, const int64_t *
         SGC_HIP_CHECK(hipGetLastError());
         for (int32_t it = 0; it < max_iter; ++it) {
             float *loss = (it == 0 && loss_trace) ? loss_trace + step : loss_slot;
-            if (const int rc = xent_closure(stop, X, ldx, W, b, labels, M, K, C, loss, grad,
-                                            b ? grad + ck : nullptr, xent_ws, s))
+            if (const int rc = closure(stop, loss, grad, b ? grad + ck : nullptr, xent_ws))
                 return rc;
             const hipError_t e = enqueue_iterate(st, T, n, loss, lrf, max_iter, max_eval, tol_grad,
                                                  tol_change, s);
-            SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "train_lbfgs launch failed: %s",
+            SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "%s launch failed: %s", what,
                         hipGetErrorString(e));
         }
         if (status_trace) {
@@ -653,6 +641,66 @@ int train_lbfgs(const float *X, int64_t ldx, float *W, float *b, const int64_t *
         }
     }
     return SGC_OK;
+}
+
+int train_lbfgs(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels, int64_t M,
+                int64_t K, int64_t C, void *state, int32_t steps, double lr, int32_t max_iter,
+                int32_t max_eval, double tol_grad, double tol_change, float *loss_trace,
+                int64_t *status_trace, void *ws, int64_t ws_bytes, hipStream_t s) {
+    SGC_REQUIRE(steps >= 0, SGC_EINVAL, "train_lbfgs: steps=%d < 0", steps);
+    SGC_REQUIRE(M > 0 && K > 0 && C > 0 && C <= 64 && ldx >= K, SGC_EINVAL,
+                "train_lbfgs: bad shape M=%lld K=%lld C=%lld ldx=%lld (1 <= C <= 64, ldx >= K)",
+                (long long)M, (long long)K, (long long)C, (long long)ldx);
+    SGC_REQUIRE(max_iter >= 1, SGC_EINVAL, "train_lbfgs: max_iter=%d < 1", max_iter);
+    SGC_REQUIRE(X && W && labels && state && ws, SGC_EINVAL, "train_lbfgs: null pointer");
+    SGC_REQUIRE(reinterpret_cast<uintptr_t>(X) % 4 == 0, SGC_EINVAL,
+                "train_lbfgs: X not 4-B aligned");
+    const int64_t ck = C * K, n = ck + (b ? C : 0);
+    SGC_REQUIRE(n <= kMaxN, SGC_ERANGE, "train_lbfgs: n=%lld > %lld parameters", (long long)n,
+                (long long)kMaxN);
+    if (const int rc = xent_closure_check("train_lbfgs", M, K, C, ldx)) return rc;
+    const int64_t need = train_lbfgs_workspace(M, K, C);
+    SGC_REQUIRE(ws_bytes >= need, SGC_ENOMEM, "train_lbfgs: workspace %lld < %lld",
+                (long long)ws_bytes, (long long)need);
+    if (steps == 0) return SGC_OK;
+    auto closure = [&](const int64_t *stop, float *loss, float *dW, float *db, void *xent_ws) {
+        return xent_closure(stop, X, ldx, W, b, labels, M, K, C, loss, dW, db, xent_ws, s);
+    };
+    return run_train_steps("train_lbfgs", closure, W, b, K, C, state, steps, lr, max_iter, max_eval,
+                           tol_grad, tol_change, loss_trace, status_trace, ws, s);
+}
+
+// ---- sgc_train_lbfgs_x16: the same loop, the closure on 16-bit X ---------------
+// (xent16.hip: launches A, B and C of sgc_linear_xent_x16 behind the stop word)
+int64_t train_lbfgs_x16_workspace(int64_t M, int64_t K, int64_t C) {
+    const int64_t xw = linear_xent_x16_workspace_bytes(M, K, C);
+    if (xw == 0 || C * K + C > kMaxN) return 0;
+    return 256 + round_up((C * K + C) * 4, 256) + 256 + xw;
+}
+
+int train_lbfgs_x16(const void *X, int32_t x_dtype, int64_t ldx, float *W, float *b,
+                    const int64_t *labels, int64_t M, int64_t K, int64_t C, void *state,
+                    int32_t steps, double lr, int32_t max_iter, int32_t max_eval, double tol_grad,
+                    double tol_change, float *loss_trace, int64_t *status_trace, void *ws,
+                    int64_t ws_bytes, hipStream_t s) {
+    SGC_REQUIRE(steps >= 0, SGC_EINVAL, "train_lbfgs_x16: steps=%d < 0", steps);
+    if (const int rc = xent_x16_closure_check("train_lbfgs_x16", X, x_dtype, ldx, M, K, C))
+        return rc;
+    SGC_REQUIRE(max_iter >= 1, SGC_EINVAL, "train_lbfgs_x16: max_iter=%d < 1", max_iter);
+    SGC_REQUIRE(X && W && labels && state && ws, SGC_EINVAL, "train_lbfgs_x16: null pointer");
+    const int64_t n = C * K + (b ? C : 0);
+    SGC_REQUIRE(C * K + C <= kMaxN, SGC_ERANGE, "train_lbfgs_x16: n=%lld > %lld parameters",
+                (long long)n, (long long)kMaxN);
+    const int64_t need = train_lbfgs_x16_workspace(M, K, C);
+    SGC_REQUIRE(ws_bytes >= need, SGC_ENOMEM, "train_lbfgs_x16: workspace %lld < %lld",
+                (long long)ws_bytes, (long long)need);
+    if (steps == 0) return SGC_OK;
+    auto closure = [&](const int64_t *stop, float *loss, float *dW, float *db, void *xent_ws) {
+        return xent_x16_closure(stop, X, x_dtype, ldx, W, b, labels, M, K, C, loss, dW, db, xent_ws,
+                                s);
+    };
+    return run_train_steps("train_lbfgs_x16", closure, W, b, K, C, state, steps, lr, max_iter,
+                           max_eval, tol_grad, tol_change, loss_trace, status_trace, ws, s);
 }
 
 SGC_WARM_UNIT(warm_lbfgs)

@@ -24,6 +24,15 @@
 // aligned (every buffer range is then a whole number of dwords; b128 / b64
 // buffer loads run at 4-B alignment, as the fp32 split kernel's do at odd
 // pitches), and M * ldx * 2 < 2^31.
+//
+// Stop-aware form (sgc_train_lbfgs_x16, xent16.hip): the weight backward exists
+// a second time as xent_dw_cols_x16_stop_kernel, compiled from this text by
+// xent.hip's scheme.  xent16.hip includes this file inside namespace sgc with
+// SGC_X16_STOP_PASS defined and SGC_X16_KERNEL / _STOP_PARAM / _STOP_TEST
+// naming the second form: it then sees namespace x16's helpers and that one
+// kernel, nothing else.  Without SGC_X16_STOP_PASS the three macros leave the
+// kernel's text as it was, so this unit's device code does not change.
+#ifndef SGC_X16_STOP_PASS
 #include <algorithm>
 
 #include "gemm_tile.h"
@@ -31,7 +40,12 @@
 #include "split_bf16.h"
 #include "x16.h"
 
+#define SGC_X16_KERNEL(name) name##_kernel
+#define SGC_X16_STOP_PARAM
+#define SGC_X16_STOP_TEST
+
 namespace sgc {
+#endif  // !SGC_X16_STOP_PASS
 
 namespace x16 {
 
@@ -91,6 +105,7 @@ __host__ __device__ constexpr int half_chunks(int K) {
 
 }  // namespace x16
 
+#ifndef SGC_X16_STOP_PASS
 // ---------------------------------------------------------------------------
 // Forward, modelled on linear_split_kernel: persistent (one workgroup per
 // CU), W's three-piece operand image built in-kernel behind the first X
@@ -355,6 +370,7 @@ __global__ __launch_bounds__(64 * NW) void linear_x16_kernel(
     }
     flush();
 }
+#endif  // !SGC_X16_STOP_PASS
 
 // ---------------------------------------------------------------------------
 // Weight backward, modelled on xent_dw_cols_kernel (up to 48 classes): R row
@@ -392,8 +408,8 @@ __device__ __forceinline__ void load_floats(__amdgpu_buffer_rsrc_t r, uint32_t o
 }  // namespace x16
 
 template <int NT, typename XT>
-__global__ __launch_bounds__(256) void xent_dw_cols_x16_kernel(
-    const XT *__restrict__ X, int64_t ldx, const float *__restrict__ G, int ldg, int M, int K,
+__global__ __launch_bounds__(256) void SGC_X16_KERNEL(xent_dw_cols_x16)(
+    SGC_X16_STOP_PARAM const XT *__restrict__ X, int64_t ldx, const float *__restrict__ G, int ldg, int M, int K,
     int C, int n_cblk, int R, float *__restrict__ slab, float *__restrict__ db_slab) {
     using namespace x16;
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -401,6 +417,7 @@ __global__ __launch_bounds__(256) void xent_dw_cols_x16_kernel(
     constexpr int XP = kF16 ? 2 : 1;  // pieces of x
     __shared__ f32x4 red[4][NT][4][64];  // [wave][class tile][q][lane] -> N-tiles e = 0..3
     __shared__ float dbr[4][NT * 16];
+    SGC_X16_STOP_TEST
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform loop bounds
     const int i = lane & 15, g = lane >> 4;
@@ -536,6 +553,7 @@ __global__ __launch_bounds__(256) void xent_dw_cols_x16_kernel(
             ((dbr[0][threadIdx.x] + dbr[1][threadIdx.x]) + dbr[2][threadIdx.x]) + dbr[3][threadIdx.x];
 }
 
+#ifndef SGC_X16_STOP_PASS
 // ---------------------------------------------------------------------------
 namespace {
 
@@ -650,6 +668,18 @@ int launch_linear_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *
     return SGC_OK;
 }
 
+// Launch B of the fused 16-bit step (xent16.hip): the plain kernel on G, the
+// partials left for the caller's reduction.  Arguments checked by the caller.
+int dw_cols_x16_ranges(int64_t M) { return dw16_ranges(M); }
+
+hipError_t launch_dw_cols_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *G, int ldg,
+                              int M, int K, int C, float *slab, float *db_slab, hipStream_t s) {
+    const int nt = (C + 15) / 16;
+    return x_dtype == SGC_DTYPE_BF16
+               ? dispatch_dw16<bf16_t>(nt, X, ldx, G, ldg, M, K, C, slab, db_slab, s)
+               : dispatch_dw16<f16_t>(nt, X, ldx, G, ldg, M, K, C, slab, db_slab, s);
+}
+
 const char *linear_backward_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,
                                             const void *X, int32_t x_dtype) {
     if (!dtype_ok(x_dtype) || !backward_covers(M, K, ldx, C, X)) return "none";
@@ -705,3 +735,4 @@ int linear_backward_x16(const void *X, int32_t x_dtype, int64_t ldx, const float
 }
 
 }  // namespace sgc
+#endif  // !SGC_X16_STOP_PASS

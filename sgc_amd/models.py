@@ -43,8 +43,9 @@ every M: a non-finite x inside the K range gives non-finite logits in its
 row and a non-finite column of dW, not necessarily torch's +-inf (an infinite
 fp16 x splits into inf and inf - inf; an infinite x times a zero piece of w
 is NaN); no tuning selects torch's semantics for 16-bit x short of x.float().
-The fused sgc_linear_xent_f32 step stays float32-only: sgc_cross_entropy on
-16-bit features takes the unfused expression.
+sgc_cross_entropy on 16-bit features takes the unfused expression; the fused
+16-bit training step (sgc_linear_xent_x16) lives in propagate.linear_xent and
+behind optim.Adam.run_epochs / optim.LBFGS.run_steps.
 """
 import weakref
 
@@ -239,7 +240,7 @@ def sgc_cross_entropy(model, features, labels):
     reference closure, citation.py:47-49 / reddit.py:55-58).  Works with Adam
     and LBFGS exactly like the unfused expression.  CPU tensors take the
     unfused expression itself, and so do 16-bit features on either device (the
-    fused step is float32-only)."""
+    fused 16-bit step is propagate.linear_xent's)."""
     if features.device.type == "cpu" or features.dtype in (torch.bfloat16, torch.float16):
         return F.cross_entropy(model(features), labels)
     return _LinearCrossEntropy.apply(features, model.W.weight, model.W.bias, labels)

@@ -27,12 +27,18 @@ only) and one read-back of the per-step status table when: the device path
 above holds; the model is exactly sgc_amd.models.SGC with a bias and the
 optimiser's parameters are [W.weight, W.bias] in that order; the features are
 float32 on the parameters' ROCm device, 2-D with K columns (copied only where
-the layout needs it); the labels are int64 on that device, one per row, none
-of them -100; and there are at most 64 classes.  Anything else -- CPU tensors,
-bfloat16 / float16 features, rows labelled -100, strong-Wolfe, more than 64
-classes, a foreign model, another parameter order -- is the literal loop of
-step() calls.  The fused run is bit-identical to the stepwise device path
-driven with the closure `sgc_cross_entropy(model, x, y).backward()`.
+the layout needs it), or bfloat16 / float16 there in a layout
+sgc_linear_xent_x16_kernel_name covers as it lies in memory (even pitch, 4-B
+aligned base, at most 48 classes: sgc_train_lbfgs_x16, X read at 16 bits); the
+labels are int64 on that device, one per row, none of them -100; and there are
+at most 64 classes.  Anything else -- CPU tensors, 16-bit features at an odd
+pitch (no re-pitching copy is made here, unlike Adam.run_epochs: the literal
+loop is the pinned behaviour for them), rows labelled -100, strong-Wolfe, more
+than 64 classes, a foreign model, another parameter order -- is the literal
+loop of step() calls.  The fused run is bit-identical to the stepwise device
+path driven with the closure `sgc_cross_entropy(model, x, y).backward()`
+(float32 features) or with `propagate.linear_xent(x, W, b, y)` assigning
+.grad (16-bit features).
 
 Results of the device path are tolerance-equal to torch's (fp64-accumulated
 dot products in a fixed order; torch sums in fp32) and bitwise reproducible
@@ -52,6 +58,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from .propagate import X16_DTYPES, is_x16, xent_x16_layout
 
 MAX_NUMEL = 65536
 MAX_TENSORS = 16
@@ -172,7 +179,9 @@ class LBFGS(torch.optim.LBFGS):
 
     # -- whole steps in one host call ---------------------------------------------------
     def _fused_plan(self, model, features, labels):
-        """(W, b) when run_steps can run as one sgc_train_lbfgs_f32 call."""
+        """(W, b, x) when run_steps can run as one sgc_train_lbfgs_f32 /
+        sgc_train_lbfgs_x16 call on x (the features in the layout the call
+        takes)."""
         from .models import SGC
         if type(model) is not SGC or model.W.bias is None or not self.device_path():
             return None
@@ -182,7 +191,7 @@ class LBFGS(torch.optim.LBFGS):
             return None
         x, y = features, labels
         if not (isinstance(x, torch.Tensor) and x.device == W.device and
-                x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 1 and
+                (x.dtype == torch.float32 or is_x16(x)) and x.dim() == 2 and x.shape[0] >= 1 and
                 x.shape[1] == W.shape[1] and 1 <= W.shape[0] <= 64):
             return None
         if not (isinstance(y, torch.Tensor) and y.dtype == torch.int64 and y.device == x.device and
@@ -190,9 +199,17 @@ class LBFGS(torch.optim.LBFGS):
             return None
         if not (W.requires_grad and b.requires_grad):
             return None
+        x = x.detach()
+        if is_x16(x):
+            # 16-bit features: only as they lie in memory (no re-pitching copy)
+            x = xent_x16_layout(x, W.shape[0], copy=False)
+            if x is None:
+                return None
+        elif x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+            x = x.contiguous()
         if _labels_have_ignored(y, W.shape[0]):
             return None
-        return W, b
+        return W, b, x
 
     def run_steps(self, model, features, labels, steps):
         """`steps` times self.step(closure) with the reference closure --
@@ -202,7 +219,10 @@ class LBFGS(torch.optim.LBFGS):
         touched).  Afterwards `step_statuses` holds one status tuple per step
         (None for a step torch's own step() ran) and `last_status` the last.
 
-        The fused path (module docstring) is one sgc_train_lbfgs_f32 call and
+        The fused path (module docstring) is one sgc_train_lbfgs_f32 call
+        (sgc_train_lbfgs_x16 on bfloat16 / float16 features that are covered
+        as they lie in memory -- even pitch, 4-B aligned; an odd pitch runs
+        the literal loop, where Adam.run_epochs would copy once) and
         one read-back of the status table, the call's only synchronisation
         after the labels' one range check; the parameters' .grad is left None.
         Everything else runs the literal loop.  A label outside [0, C) other
@@ -230,18 +250,17 @@ class LBFGS(torch.optim.LBFGS):
         if self._dev_state is not None and self._key() != self._dev_key:
             raise ValueError("sgc_amd.optim.LBFGS: the parameter list or history_size changed "
                              "after the first step")
-        W, b = plan
+        W, b, x = plan
         self.zero_grad(set_to_none=True)
         group = self.param_groups[0]
-        x = features.detach()
-        if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
-            x = x.contiguous()
         y = labels.contiguous()
         M, K = x.shape
         C = W.shape[0]
         dev = x.device
         lib = _lib.load()
-        ws_bytes = lib.sgc_train_lbfgs_workspace(M, K, C)
+        x16 = is_x16(x)
+        ws_bytes = (lib.sgc_train_lbfgs_x16_workspace if x16 else
+                    lib.sgc_train_lbfgs_workspace)(M, K, C)
         ws = getattr(self, "_train_ws", None)
         if ws is None or ws.numel() < ws_bytes or ws.device != dev:
             ws = self._train_ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=dev)
@@ -250,12 +269,16 @@ class LBFGS(torch.optim.LBFGS):
         with torch.no_grad(), torch.cuda.device(dev):
             stream = _lib.stream_handle(dev)
             state = self._ensure_state(lib, dev, stream)
-            _lib.check(lib.sgc_train_lbfgs_f32(
-                _lib.ptr(x), x.stride(0), _lib.ptr(W), _lib.ptr(b), _lib.ptr(y), M, K, C,
-                _lib.ptr(state), steps, float(group["lr"]), group["max_iter"], group["max_eval"],
-                float(group["tolerance_grad"]), float(group["tolerance_change"]),
-                _lib.ptr(losses), _lib.ptr(table), _lib.ptr(ws), ws.numel(), stream),
-                "train_lbfgs_f32")
+            tail = (_lib.ptr(W), _lib.ptr(b), _lib.ptr(y), M, K, C, _lib.ptr(state), steps,
+                    float(group["lr"]), group["max_iter"], group["max_eval"],
+                    float(group["tolerance_grad"]), float(group["tolerance_change"]),
+                    _lib.ptr(losses), _lib.ptr(table), _lib.ptr(ws), ws.numel(), stream)
+            if x16:
+                _lib.check(lib.sgc_train_lbfgs_x16(_lib.ptr(x), X16_DTYPES[x.dtype], x.stride(0),
+                                                   *tail), "train_lbfgs_x16")
+            else:
+                _lib.check(lib.sgc_train_lbfgs_f32(_lib.ptr(x), x.stride(0), *tail),
+                           "train_lbfgs_f32")
             self.step_statuses = _read_status_trace(table)
         self.last_status = self.step_statuses[-1]
         st = self.state[self._params[0]]
@@ -437,7 +460,9 @@ class Adam(torch.optim.Adam):
 
     # -- the whole loop ---------------------------------------------------------------
     def _fused_plan(self, model, features, labels):
-        """(W, b) when run_epochs can run as one sgc_train_adam_f32 call."""
+        """(W, b, x) when run_epochs can run as one sgc_train_adam_f32 /
+        sgc_train_adam_x16 call on x (the features in the layout the call
+        takes: 16-bit features after at most one even-pitch copy)."""
         from .models import SGC
         if type(model) is not SGC or model.W.bias is None or len(self.param_groups) != 1:
             return None
@@ -450,7 +475,7 @@ class Adam(torch.optim.Adam):
             return None
         x, y = features, labels
         if not (isinstance(x, torch.Tensor) and x.device.type == "cuda" and
-                x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 1 and
+                (x.dtype == torch.float32 or is_x16(x)) and x.dim() == 2 and x.shape[0] >= 1 and
                 x.shape[1] == W.shape[1] and 1 <= W.shape[0] <= 64):
             return None
         if not (isinstance(y, torch.Tensor) and y.dtype == torch.int64 and y.device == x.device and
@@ -471,14 +496,25 @@ class Adam(torch.optim.Adam):
             return None
         if _labels_have_ignored(y, W.shape[0]):
             return None
-        return W, b
+        x = x.detach()
+        if is_x16(x):
+            x = xent_x16_layout(x, W.shape[0])  # one even-pitch copy per call where needed
+            if x is None:
+                return None
+        elif x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+            x = x.contiguous()
+        return W, b, x
 
     def run_epochs(self, model, features, labels, epochs, loss_trace=False):
         """The training loop of citation.py:44-50 -- `epochs` times zero_grad,
         F.cross_entropy(model(features), labels), backward, step -- on an
         sgc_amd.models.SGC model whose two parameters form this optimiser's
         one param group.  On ROCm float32 features with at most 64 classes it
-        is one call of sgc_train_adam_f32: no launch is issued from Python per
+        is one call of sgc_train_adam_f32, on bfloat16 / float16 features that
+        sgc_linear_xent_x16_kernel_name covers (at most 48 classes) one call
+        of sgc_train_adam_x16 after at most one even-pitch copy per call
+        (Cora's 1433 and Citeseer's 3703 are odd; LBFGS.run_steps makes no
+        such copy and runs its literal loop instead): no launch is issued from Python per
         epoch and, after the labels' one range check (once per labels tensor
         object and version), nothing synchronises with the host.
 
@@ -492,7 +528,7 @@ class Adam(torch.optim.Adam):
         later step() or run_epochs() continues from there.  The fused loop
         forms no gradient tensors: the parameters' .grad is left None.
 
-        Everything else -- CPU tensors, 16-bit features, more than 64 classes,
+        Everything else -- CPU tensors, uncovered 16-bit features, more than 64 classes,
         a bias-free or foreign model, a param group step() would hand to
         torch, rows labelled -100 -- runs the literal Python loop with
         self.step() (on the CPU bit-equal to torch.optim.Adam driving the same
@@ -513,13 +549,10 @@ class Adam(torch.optim.Adam):
                 self.step()
                 losses.append(loss.detach())
             return torch.stack(losses) if loss_trace else losses[-1]
-        W, b = plan
+        W, b, x = plan
         model.train()
         self.zero_grad(set_to_none=True)
         group = self.param_groups[0]
-        x = features.detach()
-        if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
-            x = x.contiguous()
         y = labels.contiguous()
         M, K = x.shape
         C = W.shape[0]
@@ -527,19 +560,26 @@ class Adam(torch.optim.Adam):
         sw, sb = self._init_state(W), self._init_state(b)
         step0 = int(sw["step"].tolist())
         lib = _lib.load()
-        ws_bytes = lib.sgc_train_adam_workspace(M, K, C)
+        x16 = is_x16(x)
+        ws_bytes = (lib.sgc_train_adam_x16_workspace if x16 else
+                    lib.sgc_train_adam_workspace)(M, K, C)
         ws = getattr(self, "_train_ws", None)
         if ws is None or ws.numel() < ws_bytes or ws.device != dev:
             ws = self._train_ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=dev)
         trace = torch.empty(epochs, dtype=torch.float32, device=dev)
         b1, b2 = group["betas"]
         with torch.no_grad(), torch.cuda.device(dev):
-            _lib.check(lib.sgc_train_adam_f32(
-                _lib.ptr(x), x.stride(0), _lib.ptr(W), _lib.ptr(b), _lib.ptr(y), M, K, C,
-                _lib.ptr(sw["exp_avg"]), _lib.ptr(sw["exp_avg_sq"]), _lib.ptr(sb["exp_avg"]),
-                _lib.ptr(sb["exp_avg_sq"]), step0, epochs, float(group["lr"]), float(b1),
-                float(b2), float(group["eps"]), float(group["weight_decay"]), _lib.ptr(trace),
-                _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)), "train_adam_f32")
+            tail = (_lib.ptr(W), _lib.ptr(b), _lib.ptr(y), M, K, C, _lib.ptr(sw["exp_avg"]),
+                    _lib.ptr(sw["exp_avg_sq"]), _lib.ptr(sb["exp_avg"]), _lib.ptr(sb["exp_avg_sq"]),
+                    step0, epochs, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                    float(group["weight_decay"]), _lib.ptr(trace), _lib.ptr(ws), ws.numel(),
+                    _lib.stream_handle(dev))
+            if x16:
+                _lib.check(lib.sgc_train_adam_x16(_lib.ptr(x), X16_DTYPES[x.dtype], x.stride(0),
+                                                  *tail), "train_adam_x16")
+            else:
+                _lib.check(lib.sgc_train_adam_f32(_lib.ptr(x), x.stride(0), *tail),
+                           "train_adam_f32")
         for st in (sw, sb):
             st["step"] += epochs
         return trace if loss_trace else trace[-1]

@@ -1430,13 +1430,48 @@ def linear_backward(X: torch.Tensor, grad_out: torch.Tensor, want_bias=True):
     return dW, db
 
 
+def xent_x16_layout(X, C, copy=True):
+    """A 16-bit X as the fused 16-bit step (sgc_linear_xent_x16) takes it, or
+    None where sgc_linear_xent_x16_kernel_name does not cover it: X itself
+    where it is covered as it lies in memory; with `copy`, a layout problem
+    alone (odd element pitch, 2-B-aligned base) is fixed by one
+    _even_pitch_x16 copy, the rule `linear` follows."""
+    lib = _lib.load()
+    M, K = X.shape
+    dt = X16_DTYPES[X.dtype]
+
+    def named(t):
+        return lib.sgc_linear_xent_x16_kernel_name(M, K, t.stride(0), C, _lib.ptr(t),
+                                                   dt) != b"none"
+
+    if M == 0:
+        return None
+    if X.stride(1) == 1 and X.stride(0) >= K and named(X):
+        return X
+    if not copy or C > 48:
+        return None
+    X = _even_pitch_x16(X)
+    return X if named(X) else None
+
+
 def linear_xent(X: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
                 labels: torch.Tensor, want_logits=False):
     """Fused SGC training step: (loss, dW, db[, logits]) for
-    F.cross_entropy(X W^T + b, labels) (mean), on the GPU (sgc_linear_xent_f32)."""
+    F.cross_entropy(X W^T + b, labels) (mean), on the GPU; everything returned
+    is float32.
+
+    float32 X runs sgc_linear_xent_f32.  torch.bfloat16 / torch.float16 X gives
+    the step on the exactly widened elements, X read twice at 16 bits
+    (sgc_linear_xent_x16), where sgc_linear_xent_x16_kernel_name covers it --
+    after one even-pitch copy where the layout alone is the problem (an odd
+    pitch such as 1433 or 3703, a 2-B-aligned base); anything still uncovered
+    (more than 48 classes, W's image past LDS, offsets past 31 bits) takes
+    X.float() and the float32 step.  want_logits on 16-bit X takes the logits
+    from `linear` (the fused 16-bit step forms none)."""
     _require_device(X, "input")
-    if X.dtype != torch.float32 or weight.dtype != torch.float32:
-        raise TypeError("sgc_amd.linear_xent: float32 only")
+    if not (X.dtype == torch.float32 or is_x16(X)) or weight.dtype != torch.float32:
+        raise TypeError("sgc_amd.linear_xent: float32, bfloat16 or float16 features and float32 "
+                        "weights only")
     M, K = X.shape
     C = weight.shape[0]
     if weight.shape[1] != K or labels.shape != (M,):
@@ -1460,6 +1495,18 @@ def linear_xent(X: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     loss = torch.empty((), dtype=torch.float32, device=X.device)
     dW = torch.empty_like(W)
     db = torch.empty(C, dtype=torch.float32, device=X.device) if b is not None else None
+    if is_x16(X):
+        X16 = xent_x16_layout(X, C)
+        if X16 is not None:
+            ws_bytes = lib.sgc_linear_xent_x16_workspace(M, K, C)
+            ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=X.device)
+            with torch.cuda.device(X.device):
+                _lib.check(lib.sgc_linear_xent_x16(
+                    _lib.ptr(X16), X16_DTYPES[X16.dtype], X16.stride(0), _lib.ptr(W), _lib.ptr(b),
+                    _lib.ptr(y), M, K, C, _lib.ptr(loss), _lib.ptr(dW), _lib.ptr(db), _lib.ptr(ws),
+                    ws_bytes, _lib.stream_handle(X.device)), "linear_xent_x16")
+            return (loss, dW, db, linear(X16, W, b)) if want_logits else (loss, dW, db)
+        X = X.float()  # not covered: the float32 step on the widened copy
     logits = torch.empty((M, C), dtype=torch.float32, device=X.device) if want_logits else None
     ws_bytes = lib.sgc_linear_xent_workspace(M, K, C)
     ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=X.device)
