@@ -125,9 +125,12 @@ int64_t sgc_get_tuning(const char *key);
  *
  * sgc_coo_to_csr_workspace: bytes of device scratch sgc_coo_to_csr needs.
  * sgc_coo_to_csr: rows/cols are the two rows of the [2,nnz] index tensor.
- *   status_host (synchronous; may be NULL to stay asynchronous) receives a
- *   bit set: 1 = input rows already sorted, 2 = every CSR row has strictly
- *   ascending columns, 4 = an index was out of range (CSR then invalid).
+ *   status_host (may be NULL: the call is synchronous either way, it reads
+ *   its flags back to choose the sorted or the unsorted path and to return
+ *   SGC_ERANGE) receives a bit set: 1 = input rows already sorted, 2 = every
+ *   CSR row has strictly ascending columns (of the CSR written, whether or
+ *   not the input rows were sorted), 4 = an index was out of range (CSR then
+ *   invalid).
  * ------------------------------------------------------------------------- */
 int sgc_coo_to_csr_workspace(int64_t n_rows, int64_t nnz, size_t *bytes_host);
 int sgc_coo_to_csr(const int64_t *rows, const int64_t *cols, const float *vals,
@@ -136,7 +139,11 @@ int sgc_coo_to_csr(const int64_t *rows, const int64_t *cols, const float *vals,
                    void *workspace, size_t workspace_bytes,
                    uint32_t *status_host, void *stream);
 
-/* Same, from torch CSR (crow_indices/col_indices int64): narrows to int32. */
+/* Same, from torch CSR (crow_indices/col_indices int64): narrows to int32.
+ * Status bit 1 is always set, bit 2 as above.  SGC_ERANGE with bit 4 for a
+ * column outside [0, n_cols) and for a crow that is no layout of the nnz
+ * entries: an element outside [0, nnz], a decrease, crow[0] != 0 or
+ * crow[n_rows] != nnz. */
 int sgc_csr64_to_csr(const int64_t *crow, const int64_t *col, const float *vals,
                      int64_t nnz, int64_t n_rows, int64_t n_cols,
                      int32_t *row_ptr, int32_t *col_idx, float *val_out,

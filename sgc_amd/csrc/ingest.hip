@@ -107,7 +107,11 @@ __global__ void csr64_narrow_kernel(const int64_t *__restrict__ crow, const int6
          k += (int64_t)gridDim.x * blockDim.x) {
         if (k <= n_rows) {
             const int64_t p = crow[k];
-            if (p < 0 || p > nnz || (k > 0 && crow[k - 1] > p)) atomicOr(flags, kOutOfRange);
+            // the ends too: a crow that skips leading or trailing entries is
+            // no layout of these nnz entries
+            if (p < 0 || p > nnz || (k > 0 && crow[k - 1] > p) || (k == 0 && p != 0) ||
+                (k == n_rows && p != nnz))
+                atomicOr(flags, kOutOfRange);
             row_ptr[k] = (int32_t)p;
         }
         if (k < nnz) {
@@ -212,6 +216,12 @@ int coo_to_csr(const int64_t *rows, const int64_t *cols, const float *vals, int6
         hipLaunchKernelGGL(row_ptr_from_sorted_kernel<uint32_t>, dim3(grid_for(nnz + 1)),
                            dim3(kBlock), 0, stream, keys_out, nnz, n_rows, row_ptr);
         SGC_HIP_CHECK(hipGetLastError());
+        // check_narrow_kernel cleared kColsAscending with kRowsSorted: it saw
+        // the COO order.  The bit describes the CSR, so it starts set again
+        // and the kernel below clears it from the rows as they now are.
+        const uint32_t sorted_init = f | kColsAscending;
+        SGC_HIP_CHECK(hipMemcpyAsync(flags, &sorted_init, sizeof(sorted_init),
+                                     hipMemcpyHostToDevice, stream));
         hipLaunchKernelGGL(csr_cols_ascending_kernel, dim3(grid_for(n_rows)), dim3(kBlock), 0,
                            stream, row_ptr, col_idx, n_rows, flags);
         SGC_HIP_CHECK(hipGetLastError());

@@ -221,10 +221,7 @@ def check_coo_ingest(rows, cols, shape):
     same_row = np.diff(rows[order]) == 0
     ascending = bool(np.all(np.diff(cols[order])[same_row] > 0))
     assert bool(csr.status & STATUS_ROWS_SORTED) == rows_sorted
-    if rows_sorted:
-        assert bool(csr.status & STATUS_COLS_ASCENDING) == ascending
-    else:   # after a sort the bit may stay clear, but it never claims what is not so
-        assert ascending or not csr.status & STATUS_COLS_ASCENDING
+    assert bool(csr.status & STATUS_COLS_ASCENDING) == ascending   # of the CSR, sorted input or not
     assert not csr.status & 4
     return csr
 
