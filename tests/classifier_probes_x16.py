@@ -67,12 +67,17 @@ def x16_product_model(x, w, dtype, drop=None):
     return acc_h + acc_l
 
 
-def full_mantissa_x16(g, shape, dtype):
+def full_mantissa_x16(g, shape, dtype, emin=None, emax=None):
     """`dtype` values of random sign with every mantissa bit random and the
     lowest set (bf16: 7 bits, fp16: 10 -- an fp16 value then has a non-zero m
     piece), exponents away from both types' subnormals: [-20, 20) for bf16,
-    [-10, 10) for fp16."""
-    nbits, emin, emax = (7, -20, 20) if dtype == torch.bfloat16 else (10, -10, 10)
+    [-10, 10) for fp16, or [emin, emax) where both are given."""
+    nbits, lo, hi = (7, -20, 20) if dtype == torch.bfloat16 else (10, -10, 10)
+    assert (emin is None) == (emax is None)
+    if emin is not None:
+        assert lo <= emin < emax <= hi
+    else:
+        emin, emax = lo, hi
     mant = torch.randint(0, 1 << nbits, shape, generator=g, dtype=torch.int64) | 1
     expo = torch.randint(emin, emax, shape, generator=g, dtype=torch.int64) + 127
     sign = torch.randint(0, 2, shape, generator=g, dtype=torch.int64)
