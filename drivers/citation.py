@@ -4,6 +4,7 @@ lines), reading Planetoid files from ./data like the reference.
 
     python drivers/citation.py --dataset cora [--tuned] [--degree 2] [--epochs 100]
                                [--feature-dtype {float32,bfloat16,float16}] [--device-adam]
+                               [--device-eval]
 
 Flow (reference citation.py:14-70): seed -> load_citation -> SGC model
 (created before the precompute, so the RNG draws for W match) ->
@@ -19,6 +20,10 @@ the loop below runs through torch.optim.Adam as before.  The two combine:
 --feature-dtype bfloat16 --device-adam trains on the 16-bit rows in one host
 call too (sgc_train_adam_x16; an odd feature count such as Cora's 1433 costs
 one even-pitch copy of the training rows per call).
+--device-eval (this driver's own as well) takes the validation and the test
+accuracy from model.evaluate: one launch chain per split that reads the rows
+once and leaves the counts on the GPU, in place of accuracy(model(x), y); the
+printed lines keep their format and values.
 """
 import argparse
 import os
@@ -41,7 +46,7 @@ TUNED_WEIGHT_DECAY = {"cora": 1.3027e-05, "citeseer": 2.3546e-05, "pubmed": 7.40
 
 
 def train_regression(model, train_features, train_labels, val_features, val_labels,
-                     epochs, weight_decay, lr, dropout, device_adam=False):
+                     epochs, weight_decay, lr, dropout, device_adam=False, device_eval=False):
     if device_adam:  # the whole loop below in one host call (sgc_amd/optim.py)
         from sgc_amd.optim import Adam
         optimizer = Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
@@ -61,12 +66,17 @@ def train_regression(model, train_features, train_labels, val_features, val_labe
     train_time = perf_counter() - t
     with torch.no_grad():
         model.eval()
-        acc_val = accuracy(model(val_features), val_labels)
+        if device_eval:
+            acc_val = model.evaluate(val_features, val_labels).accuracy()
+        else:
+            acc_val = accuracy(model(val_features), val_labels)
     return model, acc_val, train_time
 
 
-def test_regression(model, test_features, test_labels):
+def test_regression(model, test_features, test_labels, device_eval=False):
     model.eval()
+    if device_eval:  # the counts on the GPU, no logits (SGC.evaluate)
+        return model.evaluate(test_features, test_labels).accuracy()
     return accuracy(model(test_features), test_labels)
 
 
@@ -79,6 +89,9 @@ def parse_own(argv=None):
     own.add_argument("--device-adam", action="store_true", default=False,
                      help="train with sgc_amd.optim.Adam.run_epochs (the epochs in one host call, "
                           "on float32, bfloat16 or float16 features)")
+    own.add_argument("--device-eval", action="store_true", default=False,
+                     help="take the validation and test accuracy from model.evaluate (fused "
+                          "forward, argmax and counts on the GPU; no logits matrix)")
     return own.parse_known_args(argv)[0]
 
 
@@ -103,8 +116,10 @@ def main(argv=None):
     model, acc_val, train_time = train_regression(
         model, features[idx_train], labels[idx_train], features[idx_val], labels[idx_val],
         args.epochs, args.weight_decay, args.lr, args.dropout,
-        **({"device_adam": True} if own_args.device_adam else {}))  # (absent: the call as before)
-    acc_test = test_regression(model, features[idx_test], labels[idx_test])
+        **({"device_adam": True} if own_args.device_adam else {}),  # (absent: the call as before)
+        **({"device_eval": True} if own_args.device_eval else {}))
+    acc_test = test_regression(model, features[idx_test], labels[idx_test],
+                               **({"device_eval": True} if own_args.device_eval else {}))
     print("Validation Accuracy: {:.4f} Test Accuracy: {:.4f}".format(acc_val, acc_test))
     print("Pre-compute time: {:.4f}s, train time: {:.4f}s, total: {:.4f}s".format(
         precompute_time, train_time, precompute_time + train_time))

@@ -929,6 +929,80 @@ int sgc_train_lbfgs_x16(const void *X, int32_t x_dtype, int64_t ldx, float *W, f
                         void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Device-resident evaluation: what the reference's test_regression takes from
+ * model(x) -- accuracy(output, labels) (citation.py:64-66), f1(output, labels)
+ * (reddit.py:69-71), and the mean cross-entropy TextSGC's eval_linear adds --
+ * from one launch chain that reads X once (at 16 bits where X is 16-bit) and
+ * never forms the [M, C] logits:
+ *     pred[m]         = argmax_c z[m, c],  z = X W^T + b         int64 [M]
+ *     confusion[y][p] = #{m : labels[m] = y, pred[m] = p}         int64 [C][C]
+ *                       (row = label, column = prediction: sklearn's layout)
+ *     counts          = {rows counted, rows with pred = label}    int64 [2]
+ *     loss            = mean_m [ (max_c z - z[y_m]) + log sum_c exp(z - max) ]
+ * Accuracy is counts[1] / counts[0] (the matrix's trace over its sum); micro
+ * and macro F1 follow from the matrix (sgc_amd.metrics.f1_from_confusion).
+ *
+ * Argmax rule: torch's max(1)[1] -- the smallest class index whose logit no
+ * other class exceeds; a NaN logit counts as greater than everything, so the
+ * first NaN wins; -0 and +0 tie.
+ *
+ * Launches: A the forward (sgc_linear_xent_f32's launch A for fp32 X: fp32 MFMA
+ * on the 128-row LDS tile, any 4-B-aligned X; sgc_linear_x16's persistent
+ * split-bf16 stream for 16-bit X) with the row epilogue for the argmax and the
+ * loss term, storing 8 bytes per row; B labels x predictions into
+ * workgroup-local LDS integer counters, one partial table per workgroup; C the
+ * tables summed in workgroup order and the loss partials (double; one per
+ * wave for fp32, ONE PER 16-ROW TILE indexed by tile number for 16-bit X, whose
+ * waves take tiles dynamically) in a fixed order.  B is skipped without
+ * confusion and counts, B and C without labels.
+ *
+ * Arguments: b may be NULL.  labels NULL means predictions only: confusion,
+ * counts and loss must then be NULL.  Each of pred, confusion, counts and loss
+ * may be NULL on its own (all four NULL is SGC_EINVAL).  A label outside
+ * [0, C) leaves its row out of the matrix and the counts and makes the loss
+ * NaN; it never indexes the matrix.  Every pointer is a device pointer.
+ *
+ * Coverage: the two name functions are the authority (host only, they
+ * dereference nothing, "none" outside coverage).
+ *   _f32: 1 <= C <= 64, ldx >= K, X 4-B aligned, M * ldx * 4 < 2^31
+ *         (sgc_linear_xent_f32's limits);
+ *   _x16: what sgc_linear_x16_kernel_name covers (bf16 or fp16, even ldx >= K,
+ *         X 4-B aligned, M * ldx * 2 < 2^31, W's image within LDS) and
+ *         C <= 64: one class block (K = 602 gives C <= 42).
+ * Outside coverage the calls return SGC_EINVAL, and SGC_ENOMEM for a short
+ * workspace, with an sgc_last_error text before any pointer is touched; there
+ * is no other kernel behind these entries.  The workspace functions return 0
+ * where no layout of (M, K, C) is covered.
+ *
+ * Contracts: asynchronous on `stream`, no host synchronisation, no
+ * allocation, no atomics on global memory; the integer outputs are exact and
+ * the loss is summed in a fixed order: every output is bitwise reproducible run
+ * to run.  Logits within the classifier's fp32 tolerance of torch (rows whose
+ * two largest logits lie closer than that may take either class); the loss
+ * within rtol 1e-5.  A non-finite x follows the deviation documented for
+ * sgc_linear_x16 / the split kernels: its row's prediction is then some class
+ * in [0, C) and nothing else is disturbed.  The workspace holds the loss
+ * partials, the counter tables and 8 M bytes of predictions that the counting
+ * launch reads when the caller passes no `pred`; nothing of size M * C exists
+ * anywhere in the call.  The two units are not part of sgc_warmup: a process's
+ * first call pays their code-object load.
+ * ------------------------------------------------------------------------- */
+int64_t sgc_linear_eval_workspace(int64_t M, int64_t K, int64_t C);
+int sgc_linear_eval_f32(const float *X, int64_t ldx, const float *W, const float *b,
+                        const int64_t *labels, int64_t M, int64_t K, int64_t C,
+                        int64_t *pred, int64_t *confusion, int64_t *counts, float *loss,
+                        void *workspace, int64_t workspace_bytes, void *stream);
+const char *sgc_linear_eval_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,
+                                        const float *X);
+int64_t sgc_linear_eval_x16_workspace(int64_t M, int64_t K, int64_t C);
+int sgc_linear_eval_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *W, const float *b,
+                        const int64_t *labels, int64_t M, int64_t K, int64_t C,
+                        int64_t *pred, int64_t *confusion, int64_t *counts, float *loss,
+                        void *workspace, int64_t workspace_bytes, void *stream);
+const char *sgc_linear_eval_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,
+                                            const void *X, int32_t x_dtype);
+
+/* ---------------------------------------------------------------------------
  * Host (CPU) twins, for CPU tensors: the reference runs utils.py:92-97 on the
  * CPU whenever CUDA is off (args.py:39 --no-cuda; load_citation(cuda=False)).
  * Every pointer here is a HOST pointer; the calls are synchronous and

@@ -165,6 +165,14 @@ SIGNATURES = {
     "sgc_train_lbfgs_x16": (ctypes.c_int, [_p, _i32, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _i32,
                                            ctypes.c_double, _i32, _i32, ctypes.c_double,
                                            ctypes.c_double, _p, _p, _p, _i64, _p]),
+    "sgc_linear_eval_workspace": (_i64, [_i64, _i64, _i64]),
+    "sgc_linear_eval_f32": (ctypes.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p,
+                                           _p, _i64, _p]),
+    "sgc_linear_eval_kernel_name": (ctypes.c_char_p, [_i64, _i64, _i64, _i64, _p]),
+    "sgc_linear_eval_x16_workspace": (_i64, [_i64, _i64, _i64]),
+    "sgc_linear_eval_x16": (ctypes.c_int, [_p, _i32, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p,
+                                           _p, _p, _i64, _p]),
+    "sgc_linear_eval_x16_kernel_name": (ctypes.c_char_p, [_i64, _i64, _i64, _i64, _p, _i32]),
 }
 
 ABI_VERSION = 1

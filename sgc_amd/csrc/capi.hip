@@ -699,6 +699,40 @@ int sgc_train_lbfgs_x16(const void *X, int32_t x_dtype, int64_t ldx, float *W, f
                            workspace, workspace_bytes, as_stream(stream));
 }
 
+int64_t sgc_linear_eval_workspace(int64_t M, int64_t K, int64_t C) {
+    return linear_eval_workspace_bytes(M, K, C);
+}
+
+int sgc_linear_eval_f32(const float *X, int64_t ldx, const float *W, const float *b,
+                        const int64_t *labels, int64_t M, int64_t K, int64_t C, int64_t *pred,
+                        int64_t *confusion, int64_t *counts, float *loss, void *workspace,
+                        int64_t workspace_bytes, void *stream) {
+    return linear_eval_f32(X, ldx, W, b, labels, M, K, C, pred, confusion, counts, loss, workspace,
+                           workspace_bytes, as_stream(stream));
+}
+
+const char *sgc_linear_eval_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,
+                                        const float *X) {
+    return linear_eval_kernel_name(M, K, ldx, C, X);
+}
+
+int64_t sgc_linear_eval_x16_workspace(int64_t M, int64_t K, int64_t C) {
+    return linear_eval_x16_workspace_bytes(M, K, C);
+}
+
+int sgc_linear_eval_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *W, const float *b,
+                        const int64_t *labels, int64_t M, int64_t K, int64_t C, int64_t *pred,
+                        int64_t *confusion, int64_t *counts, float *loss, void *workspace,
+                        int64_t workspace_bytes, void *stream) {
+    return linear_eval_x16(X, x_dtype, ldx, W, b, labels, M, K, C, pred, confusion, counts, loss,
+                           workspace, workspace_bytes, as_stream(stream));
+}
+
+const char *sgc_linear_eval_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,
+                                            const void *X, int32_t x_dtype) {
+    return linear_eval_x16_kernel_name(M, K, ldx, C, X, x_dtype);
+}
+
 int sgc_warmup(uint32_t units, void *stream) {
     SGC_REQUIRE((units & ~7u) == 0, SGC_EINVAL, "warmup: unknown unit bits 0x%x", units);
     hipStream_t s = as_stream(stream);

@@ -234,6 +234,35 @@ int train_lbfgs_x16(const void *X, int32_t x_dtype, int64_t ldx, float *W, float
                     int32_t steps, double lr, int32_t max_iter, int32_t max_eval, double tol_grad,
                     double tol_change, float *loss_trace, int64_t *status_trace, void *ws,
                     int64_t ws_bytes, hipStream_t s);
+// eval.hip / eval16.hip: device-resident evaluation (sgc_linear_eval_f32 / _x16).
+// Shared by the two units: the workspace (loss partials, counter tables, the
+// predictions the counts read when the caller passes no `pred`), the pointer
+// rules, and the counting and finishing launches behind either forward.
+struct EvalParts {
+    double *loss_part;
+    int32_t *count_part;
+    int64_t *pred;
+};
+int64_t eval_workspace_bytes(int64_t M, int64_t C, int64_t n_loss);
+EvalParts eval_carve(void *ws, int64_t M, int64_t C, int64_t n_loss);
+int eval_check_outputs(const char *what, const int64_t *labels, const int64_t *pred,
+                       const int64_t *confusion, const int64_t *counts, const float *loss);
+int eval_count_finish(const int64_t *labels, const int64_t *pred, int64_t M, int64_t C,
+                      const EvalParts &o, int n_loss, int64_t *confusion, int64_t *counts,
+                      float *loss, hipStream_t s);
+const char *linear_eval_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C, const float *X);
+int64_t linear_eval_workspace_bytes(int64_t M, int64_t K, int64_t C);
+int linear_eval_f32(const float *X, int64_t ldx, const float *W, const float *b,
+                    const int64_t *labels, int64_t M, int64_t K, int64_t C, int64_t *pred,
+                    int64_t *confusion, int64_t *counts, float *loss, void *ws, int64_t ws_bytes,
+                    hipStream_t s);
+const char *linear_eval_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,
+                                        const void *X, int32_t x_dtype);
+int64_t linear_eval_x16_workspace_bytes(int64_t M, int64_t K, int64_t C);
+int linear_eval_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *W, const float *b,
+                    const int64_t *labels, int64_t M, int64_t K, int64_t C, int64_t *pred,
+                    int64_t *confusion, int64_t *counts, float *loss, void *ws, int64_t ws_bytes,
+                    hipStream_t s);
 int64_t plan_sorted_workspace(int64_t n_rows);
 int64_t colsplit_workspace(int64_t n_rows, int32_t groups);
 int mgpu_init(int ndev, const int *devices);

@@ -46,6 +46,12 @@ is NaN); no tuning selects torch's semantics for 16-bit x short of x.float().
 sgc_cross_entropy on 16-bit features takes the unfused expression; the fused
 16-bit training step (sgc_linear_xent_x16) lives in propagate.linear_xent and
 behind optim.Adam.run_epochs / optim.LBFGS.run_steps.
+
+Evaluation: SGC.predict(x) and SGC.evaluate(x, labels) are this engine's own
+additions -- what test_regression takes from model(x) (citation.py:64-66,
+reddit.py:69-71) from one launch chain that forms no logits matrix and leaves
+the predictions, the confusion matrix, the counts and the mean loss on the
+device (propagate.linear_eval, sgc_linear_eval_f32 / _x16; metrics.Evaluation).
 """
 import weakref
 
@@ -55,6 +61,7 @@ import torch.nn.functional as F
 
 from .propagate import linear as _mfma_linear
 from .propagate import linear_backward as _mfma_linear_backward
+from .propagate import linear_eval as _linear_eval
 from .propagate import linear_xent as _fused_xent
 
 
@@ -260,6 +267,37 @@ class SGC(nn.Module):
             return self.W(x)
         # (a logits tensor whose F.cross_entropy runs on the HIP kernels)
         return _LinearMFMA.apply(x, self.W.weight, self.W.bias).as_subclass(SGCLogits)
+
+    @torch.no_grad()
+    def predict(self, x):
+        """model(x).max(1)[1] -- int64 [M] on x's device -- without the logits
+        matrix (propagate.linear_eval: the evaluation kernels on ROCm tensors,
+        torch ops on CPU tensors and outside their coverage)."""
+        return _linear_eval(x, self.W.weight, self.W.bias).pred
+
+    @torch.no_grad()
+    def evaluate(self, x, labels):
+        """What test_regression takes from model(x) (citation.py:64-66,
+        reddit.py:69-71), left on the device: a metrics.Evaluation whose
+        .accuracy() equals accuracy(model(x), labels) and whose .f1() equals
+        f1(model(x), labels), plus the mean cross-entropy (.loss).  One launch
+        chain reads x once and forms no logits (propagate.linear_eval).  Labels
+        are checked once per tensor object and version: one outside
+        [0, nclass) raises IndexError, as F.cross_entropy does -- torch's
+        default ignore_index -100 included: no label is skipped here."""
+        from .metrics import Evaluation
+        if labels.dim() != 1 or labels.shape[0] != x.shape[0]:
+            raise RuntimeError("SGC.evaluate: one label per row expected")
+        C = self.W.weight.shape[0]
+        try:
+            # (_check_labels excuses labels equal to its ignore_index: class 0 lies in
+            # range, so as "ignore_index" it excuses no out-of-range label)
+            _check_labels(labels, C, 0)
+        except IndexError as e:
+            raise IndexError(f"{str(e).split(' (')[0]} (classes: {C}; SGC.evaluate skips no "
+                             "label, ignore_index is not supported)") from None
+        ev = _linear_eval(x, self.W.weight, self.W.bias, labels)
+        return Evaluation(ev.confusion, ev.counts[0], ev.counts[1], ev.loss, len(labels))
 
 
 def get_model(model_opt, nfeat, nclass, nhid=0, dropout=0, cuda=True):

@@ -13,6 +13,7 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
+import torch.nn.functional as _nnf
 
 from . import _lib
 
@@ -1517,3 +1518,103 @@ def linear_xent(X: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
                                            ws_bytes, _lib.stream_handle(X.device)),
                    "linear_xent_f32")
     return (loss, dW, db, logits) if want_logits else (loss, dW, db)
+
+
+class LinearEval(NamedTuple):
+    """What `linear_eval` leaves on X's device (None where not asked for)."""
+    pred: torch.Tensor                  # int64 [M]
+    confusion: Optional[torch.Tensor]   # int64 [C, C], row = label, column = prediction
+    counts: Optional[torch.Tensor]      # int64 [2]: rows counted, rows correct
+    loss: Optional[torch.Tensor]        # float32 0-d, mean cross-entropy
+
+
+def _eval_from_logits(logits, labels):
+    """`linear_eval`'s outputs from a logits matrix with torch ops: the path of
+    CPU tensors and of shapes the evaluation kernels do not cover."""
+    C = logits.shape[1]
+    pred = logits.max(1)[1]
+    if labels is None:
+        return LinearEval(pred, None, None, None)
+    ok = (labels >= 0) & (labels < C)
+    y, p = labels[ok], pred[ok]
+    confusion = torch.bincount(y * C + p, minlength=C * C).reshape(C, C)
+    counts = torch.stack([ok.sum(), (p == y).sum()]).to(torch.int64)
+    if bool(ok.all()):
+        loss = _nnf.cross_entropy(logits.float(), labels) if len(labels) else logits.new_zeros(())
+    else:  # a label outside [0, C): the kernels' NaN
+        loss = logits.new_full((), float("nan"), dtype=torch.float32)
+    return LinearEval(pred, confusion, counts, loss.detach())
+
+
+def linear_eval(X: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                labels: Optional[torch.Tensor] = None):
+    """Evaluate the classifier z = X . W^T + b without forming z: a LinearEval
+    of the predictions (torch's z.max(1)[1]) and, with `labels`, the confusion
+    matrix (row = label, column = prediction), {rows counted, rows correct} and
+    the mean cross-entropy -- all left on X's device (the kernel path never
+    synchronises with the host; the torch-op path reads one flag back).
+
+    float32 X runs sgc_linear_eval_f32; torch.bfloat16 / torch.float16 X runs
+    sgc_linear_eval_x16 on the exactly widened elements where
+    sgc_linear_eval_x16_kernel_name covers it, after one even-pitch copy where
+    the layout alone is the problem (`linear`'s rule).  Anything still
+    uncovered (more than 64 classes, W's image past LDS, offsets past 31 bits)
+    takes the logits from `linear` and forms the same outputs with torch ops
+    (max, bincount, F.cross_entropy); CPU tensors take the torch ops as well.
+    A label outside [0, C) leaves its row out of the matrix and the counts and
+    makes the loss NaN."""
+    if weight.dtype != torch.float32 or not (X.dtype == torch.float32 or is_x16(X)):
+        raise TypeError("sgc_amd.linear_eval: float32, bfloat16 or float16 features and float32 "
+                        "weights only")
+    if X.dim() != 2:
+        raise ValueError("sgc_amd.linear_eval: 2-D input expected")
+    M, K = X.shape
+    C = weight.shape[0]
+    if weight.shape[1] != K or (labels is not None and labels.shape != (M,)):
+        raise RuntimeError("sgc_amd.linear_eval: shape mismatch")
+    W = weight.detach().contiguous()
+    b = bias.detach().contiguous() if bias is not None else None
+    y = None
+    if labels is not None:
+        y = labels.to(device=X.device, dtype=torch.int64).contiguous()
+    if X.device.type == "cpu":
+        return _eval_from_logits(_nnf.linear(X.float(), W, b), y)
+    lib = _lib.load()
+    call = None
+    if M and is_x16(X):
+        dt = X16_DTYPES[X.dtype]
+
+        def named(t):
+            return lib.sgc_linear_eval_x16_kernel_name(M, K, t.stride(0), C, _lib.ptr(t),
+                                                       dt) != b"none"
+
+        X16 = X
+        if not (X16.stride(1) == 1 and X16.stride(0) >= K and named(X16)):
+            X16 = _even_pitch_x16(X16) if C <= 64 else None  # a layout problem alone: one copy
+        if X16 is not None and named(X16):
+            ws_bytes = lib.sgc_linear_eval_x16_workspace(M, K, C)
+
+            def call(*out):
+                return lib.sgc_linear_eval_x16(_lib.ptr(X16), dt, X16.stride(0), *out)
+    elif M:
+        Xc = X if X.stride(1) == 1 and X.stride(0) >= K else X.contiguous()
+        if lib.sgc_linear_eval_kernel_name(M, K, Xc.stride(0), C, _lib.ptr(Xc)) != b"none":
+            ws_bytes = lib.sgc_linear_eval_workspace(M, K, C)
+
+            def call(*out):
+                return lib.sgc_linear_eval_f32(_lib.ptr(Xc), Xc.stride(0), *out)
+    if call is None:  # not covered (or empty): the logits, then torch ops
+        return _eval_from_logits(linear(X, W, b), y)
+    dev = X.device
+    pred = torch.empty(M, dtype=torch.int64, device=dev)
+    confusion = counts = loss = None
+    if y is not None:
+        confusion = torch.empty((C, C), dtype=torch.int64, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+    ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(call(_lib.ptr(W), _lib.ptr(b), _lib.ptr(y), M, K, C, _lib.ptr(pred),
+                        _lib.ptr(confusion), _lib.ptr(counts), _lib.ptr(loss), _lib.ptr(ws),
+                        ws_bytes, _lib.stream_handle(dev)), "linear_eval")
+    return LinearEval(pred, confusion, counts, loss)
