@@ -196,6 +196,10 @@ const char *linear_backward_kernel_name(int64_t M, int64_t K, int64_t ldx, int64
                                         const float *X);
 int launch_linear_f32(const float *X, int64_t ldx, const float *W, const float *b, float *Y,
                       int64_t ldy, int64_t M, int64_t K, int64_t C, hipStream_t stream);
+// the x_dtype of every 16-bit classifier entry (linear16.hip, xent16.hip, eval16.hip)
+inline bool dtype_ok(int32_t x_dtype) {
+    return x_dtype == SGC_DTYPE_BF16 || x_dtype == SGC_DTYPE_F16;
+}
 const char *linear_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C, const void *X,
                                    int32_t x_dtype);
 int launch_linear_x16(const void *X, int32_t x_dtype, int64_t ldx, const float *W, const float *b,

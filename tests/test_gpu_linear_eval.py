@@ -182,6 +182,42 @@ def test_random_problems_decided_rows(lib, dtype, M, K, C):
         assert abs(float(out["loss"][0]) - ref) <= 1e-5 * abs(ref), (float(out["loss"][0]), ref)
 
 
+# (M, K, C, pad), ldx = K + pad: the smallest shapes at which the x16 stream takes another path
+ONE_STREAM_SHAPES = [
+    (1, 8, 1, 0),       # one half chunk, NT = 1
+    (16, 9, 17, 1),     # the second half chunk with one live k (the kernels need an even pitch:
+                        # K = 9 is covered from ldx = 10 on, its tightest layout)
+    (37, 66, 41, 0),    # a ragged double chunk whose second half is dropped, a partial row
+    (37, 66, 41, 2),    # tile, a partial last class tile
+    (33, 130, 64, 0),   # NT = 4, every class tile full
+    (4149, 64, 17, 0),  # 260 tiles: a workgroup of a 256-CU part takes a second tile
+]
+
+
+@pytest.mark.parametrize("M,K,C,pad", ONE_STREAM_SHAPES,
+                         ids=[f"{M}x{K}x{C}-ldx{K + pad}" for (M, K, C, pad) in ONE_STREAM_SHAPES])
+@pytest.mark.parametrize("dtype", ec.DTYPES[1:], ids=DTYPE_IDS[1:])
+def test_x16_predictions_are_the_argmax_of_linear_x16_logits(lib, dtype, M, K, C, pad):
+    """The forwards are one stream: sgc_linear_eval_x16 and sgc_linear_x16 form
+    the same accH + accL + bias bits, so on random operands every row's
+    prediction is the argmax of the other entry's logits -- no decided-rows
+    filter, no tolerance.  The padding of a pitch above K holds NaN."""
+    from sgc_amd import _lib
+    g = torch.Generator().manual_seed(1000 * M + 10 * K + C)
+    X = torch.randn((M, K), generator=g).to(dtype)
+    W, b = torch.randn((C, K), generator=g), torch.randn((C,), generator=g)
+    Xd, Wd, bd = ec.cp.nan_padded(X, pad, DEV)[0], W.to(DEV), b.to(DEV)
+    assert torch.equal(Xd.cpu(), X) and Xd.stride(0) == K + pad
+    Y = torch.full((M, C), float("nan"), dtype=torch.float32, device=DEV)
+    rc = lib.sgc_linear_x16(_ptr(Xd), ec.SGC_DTYPE[dtype], Xd.stride(0), _ptr(Wd), _ptr(bd), _ptr(Y),
+                            Y.stride(0), M, K, C, _lib.stream_handle(Xd.device))
+    assert rc == 0, lib.sgc_last_error()
+    rc, out = run_abi(lib, Xd, Wd, bd, None, want=("pred",))
+    assert rc == 0, lib.sgc_last_error()
+    want = Y.cpu().max(1)[1]
+    assert torch.equal(out["pred"], want), torch.nonzero(out["pred"] != want)[:10].tolist()
+
+
 NAN, INF = float("nan"), float("inf")
 
 
