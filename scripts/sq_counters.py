@@ -20,10 +20,11 @@ import sys
 
 
 def kernel_label(name):
-    """'void sgc::(anonymous namespace)::xent_dw_kernel<2, 3, 2>(float const*, ...)'
-    -> 'xent_dw_kernel<2, 3, 2>' (the anonymous namespace's parentheses must
-    go before the argument list is cut: round 5's summaries cut at them and
-    labelled every kernel '')."""
+    """'void sgc::(anonymous namespace)::xent_dw_kernel<2, 3, 2, sgc::StopWord>(float const*, ...)'
+    -> 'xent_dw_kernel<2, 3, 2, StopWord>' (the anonymous namespace's
+    parentheses must go before the argument list is cut: round 5's summaries
+    cut at them and labelled every kernel ''; the namespace is cut from the
+    name before the template arguments, which may hold '::' of their own)."""
     k = name.replace("(anonymous namespace)::", "").replace("void ", "")
     depth, cut = 0, len(k)
     for i, ch in enumerate(k):  # the first '(' outside the template arguments
@@ -34,7 +35,8 @@ def kernel_label(name):
         elif ch == "(" and depth == 0:
             cut = i
             break
-    return k[:cut].split("::")[-1].strip() if "::" in k[:cut].split("<")[0] else k[:cut].strip()
+    head, lt, targs = k[:cut].strip().partition("<")
+    return head.split("::")[-1] + lt + targs.replace("sgc::", "")
 
 
 def main(d):

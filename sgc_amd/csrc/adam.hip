@@ -316,8 +316,6 @@ __global__ __launch_bounds__(256) void adam_small_update_kernel(
     }
 }
 
-inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
-
 bool small_eligible(int64_t M, int64_t K, int64_t C) {
     const int64_t C16 = (C + 15) / 16 * 16, n_blk = (K + kSmallBK - 1) / kSmallBK;
     return M >= 1 && M <= kSmallMaxM && C >= 1 && C <= 64 && K >= 1 && K < INT32_MAX - kSmallBK &&

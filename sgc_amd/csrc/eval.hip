@@ -33,22 +33,14 @@
 
 #include "eval.h"
 #include "gemm_tile.h"
+#include "group16.h"
 #include "internal.h"
 
 namespace sgc {
 
 namespace {
 
-__device__ __forceinline__ float group16_max(float v) {
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-    return v;
-}
-__device__ __forceinline__ float group16_sum(float v) {
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
+// (group16_max / group16_sum: group16.h)
 __device__ __forceinline__ unsigned long long group16_key(unsigned long long k) {
 #pragma unroll
     for (int m = 1; m < 16; m <<= 1) k = key_max(k, __shfl_xor(k, m, 64));
@@ -197,36 +189,21 @@ __global__ __launch_bounds__(256) void eval_finish_kernel(
     if (t == 0) *loss = (float)(red[0] * inv_m);
 }
 
-inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
-
 inline int count_blocks(int64_t M) {
     return (int)std::min<int64_t>(kCountBlocks, std::max<int64_t>(1, (M + kCountRows - 1) / kCountRows));
 }
 
-template <int V, int NT>
-hipError_t launch_fwd(const float *X, int64_t ldx, const float *W, const float *b,
+// Launch A: the (V, NT, NB) table of gemm_tile.h's dispatch_tile.
+hipError_t launch_fwd(int V, int NT, const float *X, int64_t ldx, const float *W, const float *b,
                       const int64_t *labels, int M, int K, int C, int64_t *pred, double *loss_part,
                       hipStream_t s) {
     const int blocks = (M + kLdsBM - 1) / kLdsBM;
-    if (g_tile_buffers == 1)
-        hipLaunchKernelGGL((eval_fwd_kernel<V, NT, 1>), dim3(blocks), dim3(256), 0, s, X, ldx, W, b,
-                           labels, M, K, C, pred, loss_part);
-    else
-        hipLaunchKernelGGL((eval_fwd_kernel<V, NT, 2>), dim3(blocks), dim3(256), 0, s, X, ldx, W, b,
-                           labels, M, K, C, pred, loss_part);
+    dispatch_tile(V, NT, g_tile_buffers, [&](auto v, auto nt, auto nb) {
+        hipLaunchKernelGGL(
+            (eval_fwd_kernel<decltype(v)::value, decltype(nt)::value, decltype(nb)::value>),
+            dim3(blocks), dim3(256), 0, s, X, ldx, W, b, labels, M, K, C, pred, loss_part);
+    });
     return hipGetLastError();
-}
-
-template <int V>
-hipError_t dispatch_fwd(int nt, const float *X, int64_t ldx, const float *W, const float *b,
-                        const int64_t *labels, int M, int K, int C, int64_t *pred,
-                        double *loss_part, hipStream_t s) {
-    switch (nt) {
-        case 1: return launch_fwd<V, 1>(X, ldx, W, b, labels, M, K, C, pred, loss_part, s);
-        case 2: return launch_fwd<V, 2>(X, ldx, W, b, labels, M, K, C, pred, loss_part, s);
-        case 3: return launch_fwd<V, 3>(X, ldx, W, b, labels, M, K, C, pred, loss_part, s);
-        default: return launch_fwd<V, 4>(X, ldx, W, b, labels, M, K, C, pred, loss_part, s);
-    }
 }
 
 // sgc_linear_xent_f32's limits, and every byte offset of X within 31 bits
@@ -317,20 +294,11 @@ int linear_eval_f32(const float *X, int64_t ldx, const float *W, const float *b,
     const EvalParts o = eval_carve(ws, M, C, n_loss);
     // the counts read the predictions back: the workspace's own when the caller wants none
     int64_t *p = pred ? pred : ((confusion || counts) ? o.pred : nullptr);
-    int V = 1;
-    for (int v : {4, 2})
-        if (K % v == 0 && ldx % v == 0 && (uintptr_t)X % (4 * v) == 0 && (uintptr_t)W % (4 * v) == 0) {
-            V = v;
-            break;
-        }
-    const int nt = (int)((C + 15) / 16);
     // launch A reads the labels for the loss alone (the counts are launch B's): without a
     // loss it skips the softmax and writes no partials
     const int64_t *ya = loss ? labels : nullptr;
-    const hipError_t e =
-        V == 4   ? dispatch_fwd<4>(nt, X, ldx, W, b, ya, (int)M, (int)K, (int)C, p, o.loss_part, s)
-        : V == 2 ? dispatch_fwd<2>(nt, X, ldx, W, b, ya, (int)M, (int)K, (int)C, p, o.loss_part, s)
-                 : dispatch_fwd<1>(nt, X, ldx, W, b, ya, (int)M, (int)K, (int)C, p, o.loss_part, s);
+    const hipError_t e = launch_fwd(tile_vec(K, ldx, X, W), (int)((C + 15) / 16), X, ldx, W, b, ya,
+                                    (int)M, (int)K, (int)C, p, o.loss_part, s);
     SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "linear_eval launch failed: %s", hipGetErrorString(e));
     return eval_count_finish(labels, p, M, C, o, n_loss, confusion, counts, loss, s);
 }

@@ -7,6 +7,9 @@
 // step's MFMAs (register double buffer): with only a few waves per SIMD the
 // loads' latency would otherwise sit on the critical path.
 #pragma once
+#include <cstdint>
+#include <type_traits>
+
 #include "common.h"
 
 namespace sgc {
@@ -130,6 +133,50 @@ __device__ __forceinline__ typename Vec<V>::T buffer_load_vec(__amdgpu_buffer_rs
 // addressable with 31-bit byte offsets.
 inline bool block_tile_fits(int64_t ldx, int64_t K, int64_t C) {
     return ldx < (int64_t(1) << 31) / (4 * kLdsBM) && K * C < (int64_t(1) << 29);
+}
+
+// Host side: the vector width of a kernel's loads of X (and of W, where it
+// reads one: null for the weight backward) -- 4, 2 or 1 consecutive floats at
+// their natural alignment (the k >= K tail is masked).
+inline int tile_vec(int64_t K, int64_t ldx, const float *X, const float *W) {
+    for (int v : {4, 2})
+        if (K % v == 0 && ldx % v == 0 && reinterpret_cast<uintptr_t>(X) % (4 * v) == 0 &&
+            reinterpret_cast<uintptr_t>(W) % (4 * v) == 0)
+            return v;
+    return 1;
+}
+
+// Host side: run-time (NT), (V, NT) or (V, NT, NB) as compile-time constants.
+// f is a generic callable; it receives std::integral_constant arguments and
+// names its kernel with decltype(arg)::value.  nt: 1..4 (more: 4), v: 4, 2,
+// else 1, nb: 1, else 2 (g_tile_buffers).  Every kernel over these tables is
+// chosen here; a combination a kernel does not exist for is excluded in f
+// with `if constexpr`, so that no unit gains a device symbol.
+template <int N>
+using IntC = std::integral_constant<int, N>;
+
+template <class F>
+auto dispatch_nt(int nt, F &&f) {
+    switch (nt) {
+        case 1: return f(IntC<1>{});
+        case 2: return f(IntC<2>{});
+        case 3: return f(IntC<3>{});
+        default: return f(IntC<4>{});
+    }
+}
+
+template <class F>
+auto dispatch_v_nt(int v, int nt, F &&f) {
+    return dispatch_nt(nt, [&](auto NT) {
+        return v == 4 ? f(IntC<4>{}, NT) : v == 2 ? f(IntC<2>{}, NT) : f(IntC<1>{}, NT);
+    });
+}
+
+template <class F>
+auto dispatch_tile(int v, int nt, int nb, F &&f) {
+    return dispatch_v_nt(v, nt, [&](auto V, auto NT) {
+        return nb == 1 ? f(V, NT, IntC<1>{}) : f(V, NT, IntC<2>{});
+    });
 }
 
 template <int V, int NT, int NB>

@@ -90,11 +90,14 @@ int csr_cols_ascending(const int32_t *row_ptr, const int32_t *col_idx, int64_t n
 int column_groups_rule(int64_t nnz, int64_t width);
 
 // linear.hip / xent.hip / xent_fwd_stop.hip helpers of the other classifier units
+// a workspace section's size: the next section starts 256-B aligned
+inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
 hipError_t persistent_setup(const void *kernel, int *cus);
 // xent.hip: the fixed-order reduction of the dW / db partials
 hipError_t launch_reduce_dw_db(const float *slab, int n_parts, int C, int K, int C16, float *dW,
                                const float *db_slab, float *db, hipStream_t s);
-// launch A behind the stop word: xent_fwd_stop_kernel<V, NT, g_tile_buffers> (xent_fwd_stop.hip)
+// launch A behind the stop word: xent_fwd_kernel<V, NT, g_tile_buffers, StopWord>
+// (xent_fwd.h, instantiated in xent_fwd_stop.hip)
 hipError_t launch_xent_fwd_stop(int V, int NT, const int64_t *stop, const float *X, int64_t ldx,
                                 const float *W, const float *b, const int64_t *labels, int M, int K,
                                 int C, float *G, int ldg, double *loss_part, float *db_part,

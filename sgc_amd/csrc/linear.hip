@@ -642,29 +642,17 @@ int g_tile_buffers = 1;
 
 namespace {
 
-template <int V, int NT>
-hipError_t launch_linear(const float *X, int64_t ldx, const float *W, const float *b, float *Y,
-                         int64_t ldy, int M, int K, int C, hipStream_t s) {
+// The LDS tile: the (V, NT, NB) table of gemm_tile.h's dispatch_tile.
+hipError_t launch_linear(int V, int NT, const float *X, int64_t ldx, const float *W, const float *b,
+                         float *Y, int64_t ldy, int M, int K, int C, hipStream_t s) {
+    if (NT < 1 || NT > 4) return hipErrorInvalidValue;  // (a class block is 64 classes at most)
     const int64_t blocks = (M + kLdsBM - 1) / kLdsBM;
-    if (g_tile_buffers == 1)
-        hipLaunchKernelGGL((linear_kernel<V, NT, 1>), dim3((unsigned)blocks), dim3(256), 0, s, X,
-                           ldx, W, b, Y, ldy, M, K, C);
-    else
-        hipLaunchKernelGGL((linear_kernel<V, NT, 2>), dim3((unsigned)blocks), dim3(256), 0, s, X,
-                           ldx, W, b, Y, ldy, M, K, C);
+    dispatch_tile(V, NT, g_tile_buffers, [&](auto v, auto nt, auto nb) {
+        hipLaunchKernelGGL(
+            (linear_kernel<decltype(v)::value, decltype(nt)::value, decltype(nb)::value>),
+            dim3((unsigned)blocks), dim3(256), 0, s, X, ldx, W, b, Y, ldy, M, K, C);
+    });
     return hipGetLastError();
-}
-
-template <int V>
-hipError_t dispatch_nt(int nt, const float *X, int64_t ldx, const float *W, const float *b,
-                       float *Y, int64_t ldy, int M, int K, int C, hipStream_t s) {
-    switch (nt) {
-        case 1: return launch_linear<V, 1>(X, ldx, W, b, Y, ldy, M, K, C, s);
-        case 2: return launch_linear<V, 2>(X, ldx, W, b, Y, ldy, M, K, C, s);
-        case 3: return launch_linear<V, 3>(X, ldx, W, b, Y, ldy, M, K, C, s);
-        case 4: return launch_linear<V, 4>(X, ldx, W, b, Y, ldy, M, K, C, s);
-        default: return hipErrorInvalidValue;
-    }
 }
 
 }  // namespace
@@ -851,22 +839,8 @@ int launch_linear_f32(const float *X, int64_t ldx, const float *W, const float *
             SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "linear launch failed: %s", hipGetErrorString(e));
             continue;
         }
-        int V = 1;
-        for (int v : {4, 2}) {
-            // natural alignment of every vector load (the k >= K tail is masked)
-            if (K % v == 0 && ldx % v == 0 && reinterpret_cast<uintptr_t>(X) % (4 * v) == 0 &&
-                reinterpret_cast<uintptr_t>(Wc) % (4 * v) == 0) {
-                V = v;
-                break;
-            }
-        }
-        hipError_t e;
-        if (V == 4)
-            e = dispatch_nt<4>(nt, X, ldx, Wc, bc, Yc, ldy, (int)M, (int)K, cc, stream);
-        else if (V == 2)
-            e = dispatch_nt<2>(nt, X, ldx, Wc, bc, Yc, ldy, (int)M, (int)K, cc, stream);
-        else
-            e = dispatch_nt<1>(nt, X, ldx, Wc, bc, Yc, ldy, (int)M, (int)K, cc, stream);
+        const hipError_t e = launch_linear(tile_vec(K, ldx, X, Wc), nt, X, ldx, Wc, bc, Yc, ldy,
+                                           (int)M, (int)K, cc, stream);
         SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "linear launch failed: %s", hipGetErrorString(e));
     }
     return SGC_OK;

@@ -22,136 +22,26 @@
 //                         both reductions of C in one launch, each finished
 //                         gradient element applied to W / b by Adam in place.
 //
-// Stop-aware forms (sgc_train_lbfgs_f32, lbfgs.hip): the kernels of A, B
-// (fp32 slabs and column blocks) and C exist a second time as
-// <name>_stop_kernel, which take the L-BFGS state's stop word as their first
-// argument, test it with one wave-uniform load at entry and return when it is
-// set.  They are compiled from the same text, with SGC_XENT_KERNEL /
-// _STOP_PARAM / _STOP_TEST naming the second form and only those kernels
-// visible: B and C when this file includes itself (SGC_XENT_STOP_PASS 2), A
-// when xent_fwd_stop.hip includes it (SGC_XENT_STOP_PASS 1: a unit of its
-// own, because a second set of A's kernels in this unit changed the register
-// allocation of the first).  Without SGC_XENT_STOP_PASS the three macros leave
-// the plain kernels' text as it was, so their device code does not change, and
-// the stop-aware bodies cannot drift from them.
-#ifndef SGC_XENT_STOP_PASS
+// Behind the stop word (sgc_train_lbfgs_f32, lbfgs.hip): the kernels of A, B
+// (fp32 slabs and column blocks) and C are templates on a stop policy
+// (stop_policy.h), their last template parameter and last argument.  With
+// StopWord a kernel tests the L-BFGS state's stop word with one wave-uniform
+// load at entry and returns when it is set; with NoStop the argument is empty
+// and the kernel is the plain one.  One text, so the two cannot drift.  B and
+// C are instantiated with both policies here.  A (xent_fwd.h) is instantiated
+// with NoStop here and with StopWord in xent_fwd_stop.hip: a second set of A's
+// kernels in this unit changed the register allocation of the first.
 #include "adam_update.h"
 #include "gemm_tile.h"
 #include "internal.h"
 #include "split_bf16.h"
-
-#define SGC_XENT_KERNEL(name) name##_kernel
-#define SGC_XENT_STOP_PARAM
-#define SGC_XENT_STOP_TEST
+#include "stop_policy.h"
+#include "xent_fwd.h"
 
 namespace sgc {
 
 namespace {
 
-#endif  // !SGC_XENT_STOP_PASS
-#if !defined(SGC_XENT_STOP_PASS) || SGC_XENT_STOP_PASS == 1
-__device__ __forceinline__ float group16_max(float v) {
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-    return v;
-}
-__device__ __forceinline__ float group16_sum(float v) {
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// ---- A: logits -> G, loss / dG partials ------------------------------------
-template <int V, int NT, int NB>
-__global__ __launch_bounds__(256) void SGC_XENT_KERNEL(xent_fwd)(
-    SGC_XENT_STOP_PARAM const float *__restrict__ X, int64_t ldx, const float *__restrict__ W,
-    const float *__restrict__ b, const int64_t *__restrict__ labels, int M, int K, int C,
-    float inv_m, float *__restrict__ G, int ldg, double *__restrict__ loss_part,
-    float *__restrict__ db_part, float *__restrict__ logits, int64_t ldl) {
-    __shared__ LdsTile<V, NT, NB> sm;
-    SGC_XENT_STOP_TEST
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int wave = blockIdx.x * 4 + w;
-    const int i = lane & 15, g = lane >> 4;
-    const int m_blk = blockIdx.x * kLdsBM;
-    const int m0 = m_blk + w * 32;
-    double wave_loss = 0.0;
-    float dbc[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) dbc[n] = 0.f;
-    {
-        f32x4 acc[2][NT];
-        xwt_block_tile<V, NT, NB>(X, ldx, W, M, K, C, m_blk, sm, acc);
-        float bias[NT];
-        bool valid[NT];
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            const int c = n * 16 + i;
-            valid[n] = c < C;
-            bias[n] = (valid[n] && b) ? b[c] : 0.f;
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + t * 16 + g * 4 + r;
-                const bool row_ok = m < M;  // uniform per (t, r, lane group)
-                float z[NT];
-                float mx = -INFINITY;
-#pragma unroll
-                for (int n = 0; n < NT; ++n) {
-                    z[n] = valid[n] ? acc[t][n][r] + bias[n] : -INFINITY;
-                    mx = fmaxf(mx, z[n]);
-                }
-                mx = group16_max(mx);
-                float se = 0.f;
-                float ez[NT];
-#pragma unroll
-                for (int n = 0; n < NT; ++n) {
-                    ez[n] = valid[n] ? expf(z[n] - mx) : 0.f;
-                    se += ez[n];
-                }
-                se = group16_sum(se);
-                // p = exp(z - max) / sum and loss = (max - z_y) + log(sum): as
-                // softmax itself, independent of a common offset of the row
-                // (lse = max + log(sum), rounded to ulp(|lse|), put |lse| * 6e-8
-                // into exp(z - lse) and lse - z_y; loss.hip's note)
-                const float ls = logf(se);
-                const int64_t y = row_ok ? labels[m] : -1;
-                float zy = 0.f;
-#pragma unroll
-                for (int n = 0; n < NT; ++n) {
-                    const int c = n * 16 + i;
-                    const bool is_y = (c == y);
-                    if (is_y) zy = z[n];
-                    const float p = ez[n] / se;
-                    const float gv = row_ok ? (p - (is_y ? 1.f : 0.f)) * inv_m : 0.f;
-                    if (row_ok) {
-                        G[(int64_t)m * ldg + c] = gv;
-                        if (logits && valid[n]) logits[(int64_t)m * ldl + c] = z[n];
-                    }
-                    dbc[n] += gv;
-                }
-                zy = group16_sum(zy);  // exactly one lane of the group holds z_y
-                if (row_ok && i == 0) wave_loss += (double)((mx - zy) + ls);
-            }
-    }
-    // per-wave partials: loss (lanes i==0 of each group), dG column sums
-    double l = wave_loss;
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    if (lane == 0) loss_part[wave] = l;
-#pragma unroll
-    for (int n = 0; n < NT; ++n) {
-        float s = dbc[n];
-        s += __shfl_xor(s, 16, 64);
-        s += __shfl_xor(s, 32, 64);
-        if (g == 0) db_part[(int64_t)wave * ldg + n * 16 + i] = s;
-    }
-}
-#endif  // pass 1
-
-#ifndef SGC_XENT_STOP_PASS
 #ifndef SGC_DW_SLABS
 #define SGC_DW_SLABS 512
 #endif
@@ -179,14 +69,11 @@ inline bool dw_slab_fits(int64_t rows_per, int64_t ldx, int64_t ldg) {
 // db_slab (nullable): wave 0's first column group also sums its block's G
 // rows per class (lane groups in row order, then across them) into
 // db_slab[blk][C16] -- db = sum_m G_m from the same loads, in a fixed order.
-#endif  // !SGC_XENT_STOP_PASS
-#if !defined(SGC_XENT_STOP_PASS) || SGC_XENT_STOP_PASS == 2
-template <int V, int NT, int CT>
-__global__ __launch_bounds__(256) void SGC_XENT_KERNEL(xent_dw)(
-    SGC_XENT_STOP_PARAM const float *__restrict__ X, int64_t ldx, const float *__restrict__ G,
-    int ldg, int M, int K, int C, int rows_per, float *__restrict__ slab,
-    float *__restrict__ db_slab) {
-    SGC_XENT_STOP_TEST
+template <int V, int NT, int CT, class Stop>
+__global__ __launch_bounds__(256) void xent_dw_kernel(
+    const float *__restrict__ X, int64_t ldx, const float *__restrict__ G, int ldg, int M, int K,
+    int C, int rows_per, float *__restrict__ slab, float *__restrict__ db_slab, Stop stop) {
+    if (stop.set()) return;
     using VT = typename Vec<V>::T;
     const int lane = threadIdx.x & 63;
     const int w = threadIdx.x >> 6;
@@ -313,8 +200,6 @@ __global__ __launch_bounds__(256) void SGC_XENT_KERNEL(xent_dw)(
             }
     }
 }
-#endif  // pass 2
-#ifndef SGC_XENT_STOP_PASS
 
 // ---- B': dW partial slabs on split-bf16 products (round 6) -----------------
 // The same slab decomposition as xent_dw_kernel, with the fp32 MFMA
@@ -560,16 +445,13 @@ __device__ __forceinline__ void buffer_load_floats(__amdgpu_buffer_rsrc_t r, uin
 constexpr int kDwColRanges = SGC_DW_COL_RANGES;  // row ranges (a multiple of 8: the XCD numbering)
 constexpr int kDwColWidth = 64;   // columns per block
 
-#endif  // !SGC_XENT_STOP_PASS
-#if !defined(SGC_XENT_STOP_PASS) || SGC_XENT_STOP_PASS == 2
-template <int NT>
-__global__ __launch_bounds__(256) void SGC_XENT_KERNEL(xent_dw_cols)(
-    SGC_XENT_STOP_PARAM const float *__restrict__ X, int64_t ldx, const float *__restrict__ G,
-    int ldg, int M, int K, int C, int n_cblk, int R, float *__restrict__ slab,
-    float *__restrict__ db_slab) {
+template <int NT, class Stop>
+__global__ __launch_bounds__(256) void xent_dw_cols_kernel(
+    const float *__restrict__ X, int64_t ldx, const float *__restrict__ G, int ldg, int M, int K,
+    int C, int n_cblk, int R, float *__restrict__ slab, float *__restrict__ db_slab, Stop stop) {
     __shared__ f32x4 red[4][NT][4][64];  // [wave][class tile][q][lane] -> N-tiles e = 0..3
     __shared__ float dbr[4][NT * 16];
-    SGC_XENT_STOP_TEST
+    if (stop.set()) return;
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform loop bounds
     const int i = lane & 15, g = lane >> 4;
@@ -731,45 +613,46 @@ __global__ __launch_bounds__(256) void SGC_XENT_KERNEL(xent_dw_cols)(
         db_slab[(int64_t)r * (NT * 16) + threadIdx.x] =
             ((dbr[0][threadIdx.x] + dbr[1][threadIdx.x]) + dbr[2][threadIdx.x]) + dbr[3][threadIdx.x];
 }
-#endif  // pass 2
-#ifndef SGC_XENT_STOP_PASS
 
 // ---- C: fixed-order reductions ----------------------------------------------
 // dW: a block owns 64 consecutive elements; wave w sums slabs [w*n/4, (w+1)*n/4)
 // in order (coalesced 256-B rows of each slab), then wave 0 adds the four
 // partials in order.  Deterministic; ~n/4 loads in flight per lane.
-#endif  // !SGC_XENT_STOP_PASS
-#if !defined(SGC_XENT_STOP_PASS) || SGC_XENT_STOP_PASS == 2
-__global__ __launch_bounds__(256) void SGC_XENT_KERNEL(xent_reduce_dw)(
-    SGC_XENT_STOP_PARAM const float *__restrict__ slab, int n_slabs, int C, int K, int C16,
-    float *__restrict__ dW) {
+
+// Wave w's run of the slabs for element e of dW (e < C * K), eight loads in
+// flight, added in slab order.
+__device__ __forceinline__ float slab_run_sum(const float *__restrict__ slab, int n_slabs, int K,
+                                              int C16, int64_t e, int w) {
+    const int j0 = (int)((int64_t)n_slabs * w / 4), j1 = (int)((int64_t)n_slabs * (w + 1) / 4);
+    const int64_t cls = e / K, k = e - cls * K;
+    const float *p = slab + cls * K + k;
+    const int64_t stride = (int64_t)C16 * K;
+    float s = 0.f;
+    int j = j0;
+    for (; j + 8 <= j1; j += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)(j + u) * stride];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += v[u];
+    }
+    for (; j < j1; ++j) s += p[(int64_t)j * stride];
+    return s;
+}
+
+template <class Stop>
+__global__ __launch_bounds__(256) void xent_reduce_dw_kernel(const float *__restrict__ slab,
+                                                             int n_slabs, int C, int K, int C16,
+                                                             float *__restrict__ dW, Stop stop) {
     __shared__ float part[4][64];
-    SGC_XENT_STOP_TEST
+    if (stop.set()) return;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t e = blockIdx.x * 64LL + lane;
     const int64_t total = (int64_t)C * K;
-    const int j0 = (int)((int64_t)n_slabs * w / 4), j1 = (int)((int64_t)n_slabs * (w + 1) / 4);
-    float s = 0.f;
-    if (e < total) {
-        const int64_t cls = e / K, k = e - cls * K;
-        const float *p = slab + cls * K + k;
-        const int64_t stride = (int64_t)C16 * K;
-        int j = j0;
-        for (; j + 8 <= j1; j += 8) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)(j + u) * stride];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += v[u];
-        }
-        for (; j < j1; ++j) s += p[(int64_t)j * stride];
-    }
-    part[w][lane] = s;
+    part[w][lane] = e < total ? slab_run_sum(slab, n_slabs, K, C16, e, w) : 0.f;
     __syncthreads();
     if (w == 0 && e < total) dW[e] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
 }
-#endif  // pass 2
-#ifndef SGC_XENT_STOP_PASS
 
 // dW as xent_reduce_dw_kernel, and in the same launch db: blocks past dW's
 // (one per 64 classes) sum db_slab's column over the slabs, wave w a quarter
@@ -830,17 +713,19 @@ __global__ __launch_bounds__(256) void xent_reduce_dw_db_kernel(
 
 // loss (double, block C) and db (block c < C): 256 threads per block, strided
 // partial sums then a fixed-shape LDS tree -- deterministic.
-#endif  // !SGC_XENT_STOP_PASS
-#if !defined(SGC_XENT_STOP_PASS) || SGC_XENT_STOP_PASS == 2
-__global__ __launch_bounds__(256) void SGC_XENT_KERNEL(xent_reduce_small)(
-    SGC_XENT_STOP_PARAM const double *__restrict__ loss_part, const float *__restrict__ db_part,
-    int n_waves, int C, int ldg, double inv_m, float *__restrict__ loss, float *__restrict__ db) {
+
+// One block's sum: the loss partials (is_loss, in double) or column c of the
+// dG partials (in float, then widened) -- thread t adds elements t, t + 256,
+// ... in order, then the 256-wide LDS tree.  The tree's 2 KB of LDS are the
+// helper's own (with the array passed in by its callers, a second caller
+// changed the code of the first).
+__device__ __forceinline__ double strided_tree_sum(const double *__restrict__ loss_part,
+                                                   const float *__restrict__ db_part, int n_waves,
+                                                   int ldg, int c, bool is_loss) {
     __shared__ double red[256];
-    SGC_XENT_STOP_TEST
-    const int t = threadIdx.x, c = blockIdx.x;
-    if (c < C && !db) return;
+    const int t = threadIdx.x;
     double s = 0.0;
-    if (c == C) {
+    if (is_loss) {
         for (int j = t; j < n_waves; j += 256) s += loss_part[j];
     } else {
         float f = 0.f;
@@ -853,26 +738,24 @@ __global__ __launch_bounds__(256) void SGC_XENT_KERNEL(xent_reduce_small)(
         if (t < h) red[t] += red[t + h];
         __syncthreads();
     }
-    if (t == 0) {
+    return red[0];
+}
+
+template <class Stop>
+__global__ __launch_bounds__(256) void xent_reduce_small_kernel(
+    const double *__restrict__ loss_part, const float *__restrict__ db_part, int n_waves, int C,
+    int ldg, double inv_m, float *__restrict__ loss, float *__restrict__ db, Stop stop) {
+    if (stop.set()) return;
+    const int c = blockIdx.x;
+    if (c < C && !db) return;
+    const double sum = strided_tree_sum(loss_part, db_part, n_waves, ldg, c, c == C);
+    if (threadIdx.x == 0) {
         if (c == C)
-            *loss = (float)(red[0] * inv_m);
+            *loss = (float)(sum * inv_m);
         else
-            db[c] = (float)red[0];
+            db[c] = (float)sum;
     }
 }
-#endif  // pass 2
-#ifndef SGC_XENT_STOP_PASS
-// The second pass: the kernels of B and C above once more, as <name>_stop_kernel.
-#undef SGC_XENT_KERNEL
-#undef SGC_XENT_STOP_PARAM
-#undef SGC_XENT_STOP_TEST
-#define SGC_XENT_KERNEL(name) name##_stop_kernel
-#define SGC_XENT_STOP_PARAM const int64_t *__restrict__ stop,
-#define SGC_XENT_STOP_TEST \
-    if (*stop != 0) return;
-#define SGC_XENT_STOP_PASS 2
-#include "xent.hip"
-#undef SGC_XENT_STOP_PASS
 
 // The two reductions above in one launch, with the Adam update
 // (adam_update.h) applied by the thread that holds the finished gradient
@@ -888,28 +771,11 @@ __global__ __launch_bounds__(256) void xent_reduce_adam_kernel(
     float *__restrict__ b, float *__restrict__ mb, float *__restrict__ vb, AdamCoef coef,
     float *__restrict__ loss_out) {
     __shared__ float part[4][64];
-    __shared__ double red[256];
     if ((int)blockIdx.x < dw_blocks) {
         const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
         const int64_t e = blockIdx.x * 64LL + lane;
         const int64_t total = (int64_t)C * K;
-        const int j0 = (int)((int64_t)n_slabs * w / 4), j1 = (int)((int64_t)n_slabs * (w + 1) / 4);
-        float s = 0.f;
-        if (e < total) {
-            const int64_t cls = e / K, k = e - cls * K;
-            const float *p = slab + cls * K + k;
-            const int64_t stride = (int64_t)C16 * K;
-            int j = j0;
-            for (; j + 8 <= j1; j += 8) {
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)(j + u) * stride];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) s += v[u];
-            }
-            for (; j < j1; ++j) s += p[(int64_t)j * stride];
-        }
-        part[w][lane] = s;
+        part[w][lane] = e < total ? slab_run_sum(slab, n_slabs, K, C16, e, w) : 0.f;
         __syncthreads();
         if (w == 0 && e < total) {
             const float g = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
@@ -924,26 +790,13 @@ __global__ __launch_bounds__(256) void xent_reduce_adam_kernel(
     const int t = threadIdx.x, c = (int)blockIdx.x - dw_blocks;
     if (c < C && !b) return;
     if (c == C && !loss_out) return;
-    double s = 0.0;
-    if (c == C) {
-        for (int j = t; j < n_waves; j += 256) s += loss_part[j];
-    } else {
-        float f = 0.f;
-        for (int j = t; j < n_waves; j += 256) f += db_part[(int64_t)j * C16 + c];
-        s = f;
-    }
-    red[t] = s;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (t < h) red[t] += red[t + h];
-        __syncthreads();
-    }
+    const double sum = strided_tree_sum(loss_part, db_part, n_waves, C16, c, c == C);
     if (t == 0) {
         if (c == C) {
-            *loss_out = (float)(red[0] * inv_m);
+            *loss_out = (float)(sum * inv_m);
         } else {
             float pb = b[c], m = mb[c], v = vb[c];
-            adam_update(pb, m, v, (float)red[0], coef);
+            adam_update(pb, m, v, (float)sum, coef);
             b[c] = pb;
             mb[c] = m;
             vb[c] = v;
@@ -951,48 +804,42 @@ __global__ __launch_bounds__(256) void xent_reduce_adam_kernel(
     }
 }
 
-// (stop, here and below: null for the plain kernels, else the device word the
-// stop-aware kernels test -- same grid, same arguments)
-template <int V, int NT>
-hipError_t launch_fwd(const int64_t *stop, const float *X, int64_t ldx, const float *W,
-                      const float *b, const int64_t *labels, int M, int K, int C, float *G, int ldg,
-                      double *loss_part, float *db_part, float *logits, int64_t ldl,
-                      hipStream_t s) {
-    const int blocks = (M + kLdsBM - 1) / kLdsBM;
-    if (stop)
-        return launch_xent_fwd_stop(V, NT, stop, X, ldx, W, b, labels, M, K, C, G, ldg, loss_part,
-                                    db_part, logits, ldl, s);
-    if (g_tile_buffers == 1)
-        hipLaunchKernelGGL((xent_fwd_kernel<V, NT, 1>), dim3(blocks), dim3(256), 0, s, X, ldx, W,
-                           b, labels, M, K, C, 1.0f / (float)M, G, ldg, loss_part, db_part, logits,
-                           ldl);
-    else
-        hipLaunchKernelGGL((xent_fwd_kernel<V, NT, 2>), dim3(blocks), dim3(256), 0, s, X, ldx, W,
-                           b, labels, M, K, C, 1.0f / (float)M, G, ldg, loss_part, db_part, logits,
-                           ldl);
+// The launchers: run-time V (tile_vec) and NT (class tiles) through
+// gemm_tile.h's dispatch helpers.  stop, here and below: null for the NoStop
+// kernels, else the device word the StopWord kernels test -- same grid, same
+// arguments.
+hipError_t launch_fwd(const int64_t *stop, int V, int NT, const float *X, int64_t ldx,
+                      const float *W, const float *b, const int64_t *labels, int M, int K, int C,
+                      float *G, int ldg, double *loss_part, float *db_part, float *logits,
+                      int64_t ldl, hipStream_t s) {
+    return stop ? launch_xent_fwd_stop(V, NT, stop, X, ldx, W, b, labels, M, K, C, G, ldg, loss_part,
+                                       db_part, logits, ldl, s)
+                : launch_xent_fwd(NoStop{}, V, NT, g_tile_buffers, X, ldx, W, b, labels, M, K, C, G,
+                                  ldg, loss_part, db_part, logits, ldl, s);
+}
+
+hipError_t launch_dw(const int64_t *stop, int V, int NT, const float *X, int64_t ldx,
+                     const float *G, int ldg, int M, int K, int C, int n_slabs, int rows_per,
+                     float *slab, float *db_slab, hipStream_t s) {
+    dispatch_v_nt(V, NT, [&](auto v, auto nt) {
+        constexpr int VV = decltype(v)::value, NN = decltype(nt)::value, CT = (NN >= 3) ? 2 : 4;
+        if (stop)
+            hipLaunchKernelGGL((xent_dw_kernel<VV, NN, CT, StopWord>), dim3(n_slabs), dim3(256), 0,
+                               s, X, ldx, G, ldg, M, K, C, rows_per, slab, db_slab, StopWord{stop});
+        else
+            hipLaunchKernelGGL((xent_dw_kernel<VV, NN, CT, NoStop>), dim3(n_slabs), dim3(256), 0, s,
+                               X, ldx, G, ldg, M, K, C, rows_per, slab, db_slab, NoStop{});
+    });
     return hipGetLastError();
 }
 
-template <int V, int NT>
-hipError_t launch_dw(const int64_t *stop, const float *X, int64_t ldx, const float *G, int ldg,
-                     int M, int K, int C, int n_slabs, int rows_per, float *slab, float *db_slab,
-                     hipStream_t s) {
-    constexpr int CT = (NT >= 3) ? 2 : 4;
-    if (stop)
-        hipLaunchKernelGGL((xent_dw_stop_kernel<V, NT, CT>), dim3(n_slabs), dim3(256), 0, s, stop,
-                           X, ldx, G, ldg, M, K, C, rows_per, slab, db_slab);
-    else
-        hipLaunchKernelGGL((xent_dw_kernel<V, NT, CT>), dim3(n_slabs), dim3(256), 0, s, X, ldx, G,
-                           ldg, M, K, C, rows_per, slab, db_slab);
-    return hipGetLastError();
-}
-
-template <int NT>
-hipError_t launch_dw_split(const float *X, int64_t ldx, const float *G, int ldg, int M, int K,
-                           int C, int n_slabs, int rows_per, float *slab, float *db_slab,
+hipError_t launch_dw_split(int NT, const float *X, int64_t ldx, const float *G, int ldg, int M,
+                           int K, int C, int n_slabs, int rows_per, float *slab, float *db_slab,
                            hipStream_t s) {
-    hipLaunchKernelGGL((xent_dw_split_kernel<NT>), dim3(n_slabs), dim3(256), 0, s, X, ldx, G,
-                       ldg, M, K, C, rows_per, slab, db_slab);
+    dispatch_nt(NT, [&](auto nt) {
+        hipLaunchKernelGGL((xent_dw_split_kernel<decltype(nt)::value>), dim3(n_slabs), dim3(256), 0,
+                           s, X, ldx, G, ldg, M, K, C, rows_per, slab, db_slab);
+    });
     return hipGetLastError();
 }
 
@@ -1002,19 +849,28 @@ inline int dw_col_ranges(int64_t M) {
     return (int)std::min<int64_t>(kDwColRanges, std::max<int64_t>(1, (M + 31) / 32));
 }
 
-template <int NT>
-hipError_t launch_dw_cols(const int64_t *stop, const float *X, int64_t ldx, const float *G, int ldg,
-                          int M, int K, int C, float *slab, float *db_slab, hipStream_t s) {
+// (column blocks stop at 48 classes, backward_cols: NT = 4 has no kernel and must get none)
+hipError_t launch_dw_cols(const int64_t *stop, int NT, const float *X, int64_t ldx, const float *G,
+                          int ldg, int M, int K, int C, float *slab, float *db_slab,
+                          hipStream_t s) {
     const int R = dw_col_ranges(M);
     const int n_cblk = (K + kDwColWidth - 1) / kDwColWidth;
     const int blocks = n_cblk * ((R + 7) / 8) * 8;
-    if (stop)
-        hipLaunchKernelGGL((xent_dw_cols_stop_kernel<NT>), dim3(blocks), dim3(256), 0, s, stop, X,
-                           ldx, G, ldg, M, K, C, n_cblk, R, slab, db_slab);
-    else
-        hipLaunchKernelGGL((xent_dw_cols_kernel<NT>), dim3(blocks), dim3(256), 0, s, X, ldx, G, ldg,
-                           M, K, C, n_cblk, R, slab, db_slab);
-    return hipGetLastError();
+    return dispatch_nt(NT, [&](auto nt) -> hipError_t {
+        constexpr int NN = decltype(nt)::value;
+        if constexpr (NN <= 3) {
+            if (stop)
+                hipLaunchKernelGGL((xent_dw_cols_kernel<NN, StopWord>), dim3(blocks), dim3(256), 0,
+                                   s, X, ldx, G, ldg, M, K, C, n_cblk, R, slab, db_slab,
+                                   StopWord{stop});
+            else
+                hipLaunchKernelGGL((xent_dw_cols_kernel<NN, NoStop>), dim3(blocks), dim3(256), 0, s,
+                                   X, ldx, G, ldg, M, K, C, n_cblk, R, slab, db_slab, NoStop{});
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidValue;
+        }
+    });
 }
 
 }  // namespace
@@ -1045,16 +901,8 @@ static bool backward_cols(int64_t C) {
     return (g_backward_kernel == 0 || g_backward_kernel == 3) && C <= 48;
 }
 
-int64_t xent_workspace_bytes(int64_t M, int64_t K, int64_t C) {
-    if (M <= 0 || K <= 0 || C <= 0) return 0;
-    const int64_t C16 = (C + 15) / 16 * 16;
-    const int64_t waves = (M + kLdsBM - 1) / kLdsBM * 4;
-    // dW partials: the fp32 slabs' or the column blocks' row ranges
-    const int64_t n_slabs = std::max<int64_t>(std::min<int64_t>(kDwSlabs, (M + 255) / 256),
-                                              dw_col_ranges(M));
-    auto al = [](int64_t x) { return (x + 255) / 256 * 256; };
-    return al(M * C16 * 4) + al(waves * 8) + al(waves * C16 * 4) + al(n_slabs * C16 * K * 4) + 512;
-}
+// Slabs of xent_dw_kernel for M rows: 256 rows each at least, kDwSlabs at most.
+static int64_t dw_slabs(int64_t M) { return std::min<int64_t>(kDwSlabs, (M + 255) / 256); }
 
 // Where launches A and B leave G and their partials in the workspace.
 struct XentPartials {
@@ -1062,8 +910,42 @@ struct XentPartials {
     double *loss_part;
     float *db_part;
     float *slab;
-    int C16, waves, n_parts;
+    int C16, waves, n_parts;  // n_parts: the dW partials launch B wrote
 };
+
+// The fused step's workspace: G [M][C16] | loss partials [waves] double | dG
+// column sums [waves][C16] | dW partials [slabs][C16][K], room for the fp32
+// slabs' count or the column blocks' row ranges, whichever is larger.
+// *bytes (nullable): the extent from the 256-B aligned base.
+static XentPartials xent_carve(void *ws, int64_t M, int64_t K, int64_t C, int64_t *bytes) {
+    // (64-bit sizes: the size query takes shapes no launch would)
+    const int64_t C16 = (C + 15) / 16 * 16;
+    const int64_t waves = (M + kLdsBM - 1) / kLdsBM * 4;
+    const int64_t n_slabs = std::max<int64_t>(dw_slabs(M), dw_col_ranges(M));
+    const uintptr_t base = ((uintptr_t)ws + 255) & ~uintptr_t(255);
+    XentPartials o{};
+    o.C16 = (int)C16;
+    o.waves = (int)waves;
+    int64_t at = 0;
+    o.G = (float *)(base + at);
+    at += al256(M * C16 * 4);
+    o.loss_part = (double *)(base + at);
+    at += al256(waves * 8);
+    o.db_part = (float *)(base + at);
+    at += al256(waves * C16 * 4);
+    o.slab = (float *)(base + at);
+    at += al256(n_slabs * C16 * K * 4);
+    if (bytes) *bytes = at;
+    return o;
+}
+
+int64_t xent_workspace_bytes(int64_t M, int64_t K, int64_t C) {
+    if (M <= 0 || K <= 0 || C <= 0) return 0;
+    int64_t bytes = 0;
+    xent_carve(nullptr, M, K, C, &bytes);
+    return bytes + 512;
+}
+
 static int xent_launch_ab(const int64_t *stop, const float *X, int64_t ldx, const float *W,
                           const float *b, const int64_t *labels, int64_t M, int64_t K, int64_t C,
                           float *logits, int64_t ldl, void *ws, hipStream_t s, XentPartials &out);
@@ -1081,19 +963,20 @@ static int xent_step_launches(const int64_t *stop, const float *X, int64_t ldx, 
     const int64_t ck = C * K;
     const dim3 dw_grid((unsigned)((ck + 63) / 64)), small_grid((unsigned)C + 1);
     if (stop)
-        hipLaunchKernelGGL(xent_reduce_dw_stop_kernel, dw_grid, dim3(256), 0, s, stop, part.slab,
-                           part.n_parts, (int)C, (int)K, part.C16, dW);
+        hipLaunchKernelGGL(xent_reduce_dw_kernel<StopWord>, dw_grid, dim3(256), 0, s, part.slab,
+                           part.n_parts, (int)C, (int)K, part.C16, dW, StopWord{stop});
     else
-        hipLaunchKernelGGL(xent_reduce_dw_kernel, dw_grid, dim3(256), 0, s, part.slab,
-                           part.n_parts, (int)C, (int)K, part.C16, dW);
+        hipLaunchKernelGGL(xent_reduce_dw_kernel<NoStop>, dw_grid, dim3(256), 0, s, part.slab,
+                           part.n_parts, (int)C, (int)K, part.C16, dW, NoStop{});
     SGC_HIP_CHECK(hipGetLastError());
     if (stop)
-        hipLaunchKernelGGL(xent_reduce_small_stop_kernel, small_grid, dim3(256), 0, s, stop,
+        hipLaunchKernelGGL(xent_reduce_small_kernel<StopWord>, small_grid, dim3(256), 0, s,
                            part.loss_part, part.db_part, part.waves, (int)C, part.C16,
-                           1.0 / (double)M, loss, db);
+                           1.0 / (double)M, loss, db, StopWord{stop});
     else
-        hipLaunchKernelGGL(xent_reduce_small_kernel, small_grid, dim3(256), 0, s, part.loss_part,
-                           part.db_part, part.waves, (int)C, part.C16, 1.0 / (double)M, loss, db);
+        hipLaunchKernelGGL(xent_reduce_small_kernel<NoStop>, small_grid, dim3(256), 0, s,
+                           part.loss_part, part.db_part, part.waves, (int)C, part.C16,
+                           1.0 / (double)M, loss, db, NoStop{});
     SGC_HIP_CHECK(hipGetLastError());
     return SGC_OK;
 }
@@ -1109,7 +992,7 @@ int xent_closure_check(const char *what, int64_t M, int64_t K, int64_t C, int64_
     SGC_REQUIRE(block_tile_fits(ldx, K, C), SGC_ERANGE,
                 "%s: ldx=%lld / K=%lld past the tile's 31-bit offsets", what, (long long)ldx,
                 (long long)K);
-    const int64_t n_slabs = std::min<int64_t>(kDwSlabs, (M + 255) / 256);
+    const int64_t n_slabs = dw_slabs(M);
     const int64_t rows_per = ((M + n_slabs - 1) / n_slabs + 3) / 4 * 4;
     SGC_REQUIRE(dw_slab_fits(rows_per, ldx, (C + 15) / 16 * 16), SGC_ERANGE,
                 "%s: %lld rows x ldx %lld past the dW kernel's 31-bit offsets", what,
@@ -1149,72 +1032,25 @@ static int xent_launch_ab(const int64_t *stop, const float *X, int64_t ldx, cons
                           const float *b, const int64_t *labels, int64_t M, int64_t K, int64_t C,
                           float *logits, int64_t ldl, void *ws, hipStream_t s, XentPartials &out) {
     const int NT = (int)((C + 15) / 16);
-    const int C16 = NT * 16;
-    const int waves = (int)((M + kLdsBM - 1) / kLdsBM * 4);
-    const int n_slabs = (int)std::min<int64_t>(kDwSlabs, (M + 255) / 256);
+    const int n_slabs = (int)dw_slabs(M);
     const int rows_per = (int)(((M + n_slabs - 1) / n_slabs + 3) / 4 * 4);
     SGC_REQUIRE(dw_slab_fits(rows_per, ldx, NT * 16), SGC_ERANGE,
                 "classifier dW: %d rows x ldx %lld past the kernel's 31-bit offsets", rows_per,
                 (long long)ldx);
-    auto al = [](int64_t x) { return (x + 255) / 256 * 256; };
-    char *p = (char *)(((uintptr_t)ws + 255) & ~uintptr_t(255));
-    float *G = (float *)p;
-    p += al(M * C16 * 4);
-    double *loss_part = (double *)p;
-    p += al((int64_t)waves * 8);
-    float *db_part = (float *)p;
-    p += al((int64_t)waves * C16 * 4);
-    float *slab = (float *)p;
-
+    out = xent_carve(ws, M, K, C, nullptr);
     // dW on the split-bf16 column blocks up to 48 classes (as the backward)
-    const bool cols = backward_cols(C) && dw_slab_fits(32, ldx, C16);
-    const int n_parts = cols ? dw_col_ranges(M) : n_slabs;
-    int V = 1;
-    for (int v : {4, 2})
-        if (K % v == 0 && ldx % v == 0 && (uintptr_t)X % (4 * v) == 0 && (uintptr_t)W % (4 * v) == 0) {
-            V = v;
-            break;
-        }
-    hipError_t e = hipSuccess;
-#define SGC_XENT_DISPATCH(VV)                                                                    \
-    switch (NT) {                                                                                \
-        case 1: e = launch_fwd<VV, 1>(stop, X, ldx, W, b, labels, (int)M, (int)K, (int)C, G, C16,      \
-                                      loss_part, db_part, logits, ldl, s);                       \
-            if (e == hipSuccess)                                                                 \
-                e = cols ? launch_dw_cols<1>(stop, X, ldx, G, C16, (int)M, (int)K, (int)C, slab, nullptr, s) \
-                         : launch_dw<VV, 1>(stop, X, ldx, G, C16, (int)M, (int)K, C16, n_slabs, rows_per,   \
-                                              slab, nullptr, s);                                        \
-            break;                                                                               \
-        case 2: e = launch_fwd<VV, 2>(stop, X, ldx, W, b, labels, (int)M, (int)K, (int)C, G, C16,      \
-                                      loss_part, db_part, logits, ldl, s);                       \
-            if (e == hipSuccess)                                                                 \
-                e = cols ? launch_dw_cols<2>(stop, X, ldx, G, C16, (int)M, (int)K, (int)C, slab, nullptr, s) \
-                         : launch_dw<VV, 2>(stop, X, ldx, G, C16, (int)M, (int)K, C16, n_slabs, rows_per,   \
-                                              slab, nullptr, s);                                        \
-            break;                                                                               \
-        case 3: e = launch_fwd<VV, 3>(stop, X, ldx, W, b, labels, (int)M, (int)K, (int)C, G, C16,      \
-                                      loss_part, db_part, logits, ldl, s);                       \
-            if (e == hipSuccess)                                                                 \
-                e = cols ? launch_dw_cols<3>(stop, X, ldx, G, C16, (int)M, (int)K, (int)C, slab, nullptr, s) \
-                         : launch_dw<VV, 3>(stop, X, ldx, G, C16, (int)M, (int)K, C16, n_slabs, rows_per,   \
-                                              slab, nullptr, s);                                        \
-            break;                                                                               \
-        default: e = launch_fwd<VV, 4>(stop, X, ldx, W, b, labels, (int)M, (int)K, (int)C, G, C16,     \
-                                       loss_part, db_part, logits, ldl, s);                      \
-            if (e == hipSuccess) e = launch_dw<VV, 4>(stop, X, ldx, G, C16, (int)M, (int)K, C16,    \
-                                                      n_slabs, rows_per, slab, nullptr, s);                        \
-            break;                                                                               \
-    }
-    if (V == 4) {
-        SGC_XENT_DISPATCH(4)
-    } else if (V == 2) {
-        SGC_XENT_DISPATCH(2)
-    } else {
-        SGC_XENT_DISPATCH(1)
-    }
-#undef SGC_XENT_DISPATCH
+    const bool cols = backward_cols(C) && dw_slab_fits(32, ldx, out.C16);
+    out.n_parts = cols ? dw_col_ranges(M) : n_slabs;
+    const int V = tile_vec(K, ldx, X, W);
+    hipError_t e = launch_fwd(stop, V, NT, X, ldx, W, b, labels, (int)M, (int)K, (int)C, out.G,
+                              out.C16, out.loss_part, out.db_part, logits, ldl, s);
+    // (G is [M][C16], padded classes 0: the slabs take all C16 of them)
+    if (e == hipSuccess)
+        e = cols ? launch_dw_cols(stop, NT, X, ldx, out.G, out.C16, (int)M, (int)K, (int)C, out.slab,
+                                  nullptr, s)
+                 : launch_dw(stop, V, NT, X, ldx, out.G, out.C16, (int)M, (int)K, out.C16, n_slabs,
+                             rows_per, out.slab, nullptr, s);
     SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "linear_xent launch failed: %s", hipGetErrorString(e));
-    out = XentPartials{G, loss_part, db_part, slab, C16, waves, n_parts};
     return SGC_OK;
 }
 
@@ -1255,17 +1091,18 @@ int xent_adam_epoch(const float *X, int64_t ldx, float *W, float *b, const int64
 // db = sum_m dY_m from ONE read of X -- the dW slab kernel of the fused step
 // with the caller's dY as G (classes past C masked) and the db column sums
 // taken from the same G loads, then the two fixed-order reductions.
+// Room for the largest partial count of the three kernels (fp32: <= kDwSlabs
+// slabs; split-bf16: kDwSplitRows rows each; column blocks: their row ranges).
+static int64_t backward_max_slabs(int64_t M) {
+    return std::max<int64_t>(std::max<int64_t>(dw_slabs(M), (M + kDwSplitRows - 1) / kDwSplitRows),
+                             dw_col_ranges(M));
+}
+
 int64_t linear_backward_workspace_bytes(int64_t M, int64_t K, int64_t C) {
     if (M <= 0 || K <= 0 || C <= 0) return 0;
     const int64_t C16 = (C + 15) / 16 * 16;
-    // the larger of the two kernels' slab counts (fp32: <= kDwSlabs slabs;
-    // split-bf16: kDwSplitRows rows each)
-    const int64_t n_slabs = std::max<int64_t>(
-        std::max<int64_t>(std::min<int64_t>(kDwSlabs, (M + 255) / 256),
-                          (M + kDwSplitRows - 1) / kDwSplitRows),
-        dw_col_ranges(M));
-    auto al = [](int64_t x) { return (x + 255) / 256 * 256; };
-    return al(n_slabs * C16 * K * 4) + al(n_slabs * C16 * 4) + 512;
+    const int64_t n_slabs = backward_max_slabs(M);
+    return al256(n_slabs * C16 * K * 4) + al256(n_slabs * C16 * 4) + 512;
 }
 
 int linear_backward_f32(const float *X, int64_t ldx, const float *dY, int64_t ldd, int64_t M,
@@ -1282,7 +1119,7 @@ int linear_backward_f32(const float *X, int64_t ldx, const float *dY, int64_t ld
                 (long long)ws_bytes, (long long)need);
     const int NT = (int)((C + 15) / 16);
     const int C16 = NT * 16;
-    const int max_slabs = (int)std::min<int64_t>(kDwSlabs, (M + 255) / 256);
+    const int max_slabs = (int)dw_slabs(M);
     // the split-bf16 slabs need 8-B lanes of X (K, ldx even, X 8-B aligned)
     const bool split = backward_split(K, ldx, X);
     const int64_t per = (M + max_slabs - 1) / max_slabs;
@@ -1291,78 +1128,32 @@ int linear_backward_f32(const float *X, int64_t ldx, const float *dY, int64_t ld
     SGC_REQUIRE(dw_slab_fits(rows_per, ldx, ldd), SGC_ERANGE,
                 "classifier dW: %d rows x ldx %lld past the kernel's 31-bit offsets", rows_per,
                 (long long)ldx);
-    auto al = [](int64_t x) { return (x + 255) / 256 * 256; };
     char *p = (char *)(((uintptr_t)ws + 255) & ~uintptr_t(255));
     float *slab = (float *)p;
-    p += al((int64_t)std::max<int64_t>(
-                std::max<int64_t>(max_slabs, (M + kDwSplitRows - 1) / kDwSplitRows),
-                dw_col_ranges(M)) *
-            C16 * K * 4);
+    p += al256(backward_max_slabs(M) * C16 * K * 4);
     float *db_slab = db ? (float *)p : nullptr;
-    int V = 1;
-    for (int v : {4, 2})
-        if (K % v == 0 && ldx % v == 0 && (uintptr_t)X % (4 * v) == 0) {
-            V = v;
-            break;
-        }
     hipError_t e = hipSuccess;
-    const bool cols = backward_cols(C);
     int n_parts = n_slabs;
-    if (cols) {
+    if (backward_cols(C)) {
         // a step's 32 rows are one descriptor's range
         SGC_REQUIRE(dw_slab_fits(32, ldx, ldd), SGC_ERANGE,
                     "classifier dW: 32 rows x ldx %lld past the kernel's 31-bit offsets",
                     (long long)ldx);
         n_parts = dw_col_ranges(M);
-        switch (NT) {
-            case 1: e = launch_dw_cols<1>(nullptr, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, slab,
-                                          db_slab, s); break;
-            case 2: e = launch_dw_cols<2>(nullptr, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, slab,
-                                          db_slab, s); break;
-            default: e = launch_dw_cols<3>(nullptr, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, slab,
-                                           db_slab, s); break;
-        }
+        e = launch_dw_cols(nullptr, NT, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, slab, db_slab,
+                           s);
     } else if (split) {
-        switch (NT) {
-            case 1: e = launch_dw_split<1>(X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,
-                                           rows_per, slab, db_slab, s); break;
-            case 2: e = launch_dw_split<2>(X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,
-                                           rows_per, slab, db_slab, s); break;
-            case 3: e = launch_dw_split<3>(X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,
-                                           rows_per, slab, db_slab, s); break;
-            default: e = launch_dw_split<4>(X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,
-                                            rows_per, slab, db_slab, s); break;
-        }
+        e = launch_dw_split(NT, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs, rows_per,
+                            slab, db_slab, s);
     } else {
-#define SGC_BWD_DISPATCH(VV)                                                                     \
-    switch (NT) {                                                                                \
-        case 1: e = launch_dw<VV, 1>(nullptr, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,      \
-                                     rows_per, slab, db_slab, s); break;                         \
-        case 2: e = launch_dw<VV, 2>(nullptr, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,      \
-                                     rows_per, slab, db_slab, s); break;                         \
-        case 3: e = launch_dw<VV, 3>(nullptr, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,      \
-                                     rows_per, slab, db_slab, s); break;                         \
-        default: e = launch_dw<VV, 4>(nullptr, X, ldx, dY, (int)ldd, (int)M, (int)K, (int)C, n_slabs,     \
-                                      rows_per, slab, db_slab, s); break;                        \
-    }
-        if (V == 4) {
-            SGC_BWD_DISPATCH(4)
-        } else if (V == 2) {
-            SGC_BWD_DISPATCH(2)
-        } else {
-            SGC_BWD_DISPATCH(1)
-        }
-#undef SGC_BWD_DISPATCH
+        // (no W here: X alone sets the vector width)
+        e = launch_dw(nullptr, tile_vec(K, ldx, X, nullptr), NT, X, ldx, dY, (int)ldd, (int)M,
+                      (int)K, (int)C, n_slabs, rows_per, slab, db_slab, s);
     }
     SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "linear_backward launch failed: %s",
                 hipGetErrorString(e));
     // dW and db in one launch (fixed-order sums over the slabs)
-    const int dw_blocks = (int)((C * K + 63) / 64);
-    const int db_blocks = db ? (int)((C + 3) / 4) : 0;  // a wave per class
-    hipLaunchKernelGGL(xent_reduce_dw_db_kernel, dim3((unsigned)(dw_blocks + db_blocks)),
-                       dim3(256), 0, s, slab, n_parts, (int)C, (int)K, C16, dW, db_slab, db,
-                       dw_blocks);
-    SGC_HIP_CHECK(hipGetLastError());
+    SGC_HIP_CHECK(launch_reduce_dw_db(slab, n_parts, (int)C, (int)K, C16, dW, db_slab, db, s));
     return SGC_OK;
 }
 
@@ -1379,4 +1170,3 @@ const char *linear_backward_kernel_name(int64_t M, int64_t K, int64_t ldx, int64
 SGC_WARM_UNIT(warm_xent)
 
 }  // namespace sgc
-#endif  // !SGC_XENT_STOP_PASS

@@ -229,8 +229,6 @@ __global__ __launch_bounds__(256) void xent16_reduce_kernel(
     if (t == 0) *loss = (float)(red[0] * inv_m);
 }
 
-inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
-
 template <int NT, typename XT>
 hipError_t launch_fwd(const int64_t *stop, const void *X, int64_t ldx, const float *W,
                       const float *b, const int64_t *labels, int M, int K, int C, float *G, int ldg,

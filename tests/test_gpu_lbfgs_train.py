@@ -111,6 +111,34 @@ def test_bit_equal_to_the_stepwise_run(M, K, C, layout):
     assert all(s[3] >= 1 for s in statuses)
 
 
+# SHAPES' classes give 1, 3 and 4 class tiles; these give 2, once per load width
+# of the contiguous layout: scalar, 8 B, and 16 B with a ragged second row block.
+NT2_SHAPES = [(70, 33, 17), (70, 34, 32), (130, 64, 20)]
+
+
+@pytest.mark.parametrize("M,K,C", NT2_SHAPES)
+@pytest.mark.parametrize("layout", ["contiguous", "strided", "offset"])
+def test_bit_equal_with_two_class_tiles(M, K, C, layout):
+    statuses = compare(M, K, C, layout, steps=2, max_iter=4)
+    assert all(s[3] >= 1 for s in statuses)
+
+
+@pytest.mark.parametrize("C", [3, 17, 41, 49])
+def test_bit_equal_with_two_tile_buffers(C):
+    """tile_buffers = 2 (the double-buffered LDS image of launch A), one class
+    count per number of class tiles."""
+    from sgc_amd import _lib
+    lib = _lib.load()
+    before = lib.sgc_get_tuning(b"tile_buffers")
+    assert lib.sgc_set_tuning(b"tile_buffers", 2) == 0
+    try:
+        statuses = compare(130, 34, C, steps=2, max_iter=4)
+    finally:
+        restored = lib.sgc_set_tuning(b"tile_buffers", before)
+    assert restored == 0
+    assert all(s[3] >= 1 for s in statuses)
+
+
 @pytest.mark.parametrize("value", [0, 1, 2, 3])
 def test_bit_equal_under_each_backward_kernel(value):
     from sgc_amd import _lib
