@@ -4,7 +4,7 @@ lines), reading Planetoid files from ./data like the reference.
 
     python drivers/citation.py --dataset cora [--tuned] [--degree 2] [--epochs 100]
                                [--feature-dtype {float32,bfloat16,float16}] [--device-adam]
-                               [--device-eval]
+                               [--device-eval] [--tuned-from DIR]
 
 Flow (reference citation.py:14-70): seed -> load_citation -> SGC model
 (created before the precompute, so the RNG draws for W match) ->
@@ -24,9 +24,14 @@ one even-pitch copy of the training rows per call).
 accuracy from model.evaluate: one launch chain per split that reads the rows
 once and leaves the counts on the GPU, in place of accuracy(model(x), y); the
 printed lines keep their format and values.
+--tuned-from DIR (this driver's own too) reads the weight decay from
+DIR/{model}-tuning/{dataset}.txt, the pickle drivers/tuning.py writes, as the
+reference's --tuned reads its result files (citation.py:17-21), and prints
+the same "using tuned weight decay:" line; it takes precedence over --tuned.
 """
 import argparse
 import os
+import pickle as pkl
 import sys
 from time import perf_counter
 
@@ -92,6 +97,9 @@ def parse_own(argv=None):
     own.add_argument("--device-eval", action="store_true", default=False,
                      help="take the validation and test accuracy from model.evaluate (fused "
                           "forward, argmax and counts on the GPU; no logits matrix)")
+    own.add_argument("--tuned-from", metavar="DIR", default=None,
+                     help="read the weight decay from DIR/{model}-tuning/{dataset}.txt (written "
+                          "by drivers/tuning.py)")
     return own.parse_known_args(argv)[0]
 
 
@@ -99,7 +107,15 @@ def main(argv=None):
     args = get_citation_args(argv)
     own_args = parse_own(argv)
     feature_dtype = FEATURE_DTYPES[own_args.feature_dtype]
-    if args.tuned:
+    if own_args.tuned_from is not None:  # (reference citation.py:17-21, on this engine's result)
+        if args.model != "SGC":
+            raise NotImplementedError("tuned hyper-parameters exist for SGC only")
+        path = os.path.join(own_args.tuned_from, "{}-tuning".format(args.model),
+                            "{}.txt".format(args.dataset))
+        with open(path, "rb") as f:
+            args.weight_decay = pkl.load(f)["weight_decay"]
+        print("using tuned weight decay: {}".format(args.weight_decay))
+    elif args.tuned:
         if args.model != "SGC":
             raise NotImplementedError("tuned hyper-parameters exist for SGC only")
         args.weight_decay = TUNED_WEIGHT_DECAY[args.dataset]

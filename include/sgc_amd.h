@@ -110,7 +110,16 @@ const char *sgc_last_error(void);
  *                   shape it cannot take runs the general one).  Read-only
  *                   beside it: "adam_kernel_last" = the schedule the last
  *                   call ran (1 / 2; 0 before the first) and
- *                   "adam_small_max_rows" = the small schedule's row limit.
+ *                   "adam_small_max_rows" = the small schedule's row limit,
+ *                   "adam_sweep_last" = what the last
+ *                   sgc_train_adam_sweep_f32 call ran (2 batched small, 1
+ *                   general per model, 0 none yet);
+ *   "adam_sweep_form": the second launch of sgc_train_adam_sweep_f32's batched
+ *                   small schedule, 0 = rule (split where the fused form would
+ *                   re-read at least 100 MB of partial logits per epoch),
+ *                   1 = fused (one launch), 2 = split (two launches); the same
+ *                   bits either way.  Read-only beside it:
+ *                   "adam_sweep_form_last" (1 / 2; 0 before the first).
  * sgc_get_tuning returns -1 for an unknown key. */
 int sgc_set_tuning(const char *key, int64_t value);
 int64_t sgc_get_tuning(const char *key);
@@ -854,6 +863,62 @@ int sgc_train_adam_f32(const float *X, int64_t ldx, float *W, float *b, const in
                        int64_t step0, int32_t epochs, double lr, double beta1, double beta2,
                        double eps, double weight_decay, float *loss_trace,
                        void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Weight-decay sweep: B independent SGC classifiers on the same X and labels,
+ * each with its own initial weights and its own weight decay -- the trials of
+ * the reference's tuning.py:26-33 as one batch.
+ *
+ *   sgc_train_adam_sweep_f32: sgc_train_adam_f32 for models i = 0 .. B-1 in
+ *     one host call.  W [B, C, K], b [B, C] and the four moment tensors are
+ *     contiguous stacks (b and its two moments NULL together);
+ *     weight_decay_dev is B DEVICE floats, one decay per model, which the host
+ *     never reads; loss_trace is [B, epochs] (loss_trace[i * epochs + e]) or
+ *     NULL.  1 <= B <= 4096.  For every model the updated W[i], b[i], moments
+ *     and loss trace are BIT-IDENTICAL to one sgc_train_adam_f32 call on that
+ *     model alone with weight_decay = (double)weight_decay_dev[i] on the
+ *     schedule this call ran (below); a model whose decay is 0.0f takes the
+ *     "skipped when wd == 0" path.  Asynchronous, no allocation, no atomics,
+ *     no host synchronisation, every sum in a fixed order.
+ *     Schedule: where the small schedule can take the shape (M <= 313) and
+ *     "adam_kernel" is not 1, its two launches per epoch run on a K-block x
+ *     model grid, each model on its own partial-logit area and bias copy of the
+ *     workspace ("adam_kernel" = 2 results).  The second launch has two forms
+ *     with the same results ("adam_sweep_form"): fused, where every K-block's
+ *     workgroup re-sums its model's partial logits and redoes the softmax, and
+ *     split, where one workgroup per model does that once and stores
+ *     G = (softmax - onehot) / M for a dW launch over K-block x model (three
+ *     launches per epoch).  The batched schedule holds under "adam_kernel" = 0
+ *     too, at every eligible shape: the auto rule of sgc_train_adam_f32 was
+ *     measured for one model and no crossover has been measured for a batch.
+ *     Everything else (M > 313, "adam_kernel" = 1) enqueues the general
+ *     schedule model by model ("adam_kernel" = 1 results).  The read-only
+ *     tuning word "adam_sweep_last" reports what the last call ran: 2 batched
+ *     small, 1 general per model, 0 none yet.
+ *   sgc_train_adam_sweep_workspace(B, M, K, C): bytes of `workspace`; 0 for an
+ *     empty shape, C > 64 or B outside 1..4096.
+ *   sgc_linear_eval_sweep_f32: sgc_linear_eval_f32 for B stacked models in one
+ *     host call (its launch chain once per model on the one workspace,
+ *     sgc_linear_eval_workspace(M, K, C) bytes): pred [B, M], confusion
+ *     [B, C, C], counts [B, 2], loss [B], each NULL on its own as there;
+ *     model i's outputs are bit-identical to sgc_linear_eval_f32 on model i.
+ *     Coverage and errors are sgc_linear_eval_f32's; 1 <= B <= 4096.
+ * Argument errors (B out of range, a null weight_decay_dev, ldx < K, a short
+ * workspace, b and its moments not given together) return SGC_EINVAL /
+ * SGC_ENOMEM with an sgc_last_error text before any device call.
+ * ------------------------------------------------------------------------- */
+int64_t sgc_train_adam_sweep_workspace(int64_t B, int64_t M, int64_t K, int64_t C);
+int sgc_train_adam_sweep_f32(const float *X, int64_t ldx, float *W, float *b,
+                             const int64_t *labels, int64_t B, int64_t M, int64_t K, int64_t C,
+                             float *exp_avg_W, float *exp_avg_sq_W, float *exp_avg_b,
+                             float *exp_avg_sq_b, int64_t step0, int32_t epochs, double lr,
+                             double beta1, double beta2, double eps,
+                             const float *weight_decay_dev, float *loss_trace,
+                             void *workspace, int64_t workspace_bytes, void *stream);
+int sgc_linear_eval_sweep_f32(const float *X, int64_t ldx, const float *W, const float *b,
+                              const int64_t *labels, int64_t B, int64_t M, int64_t K, int64_t C,
+                              int64_t *pred, int64_t *confusion, int64_t *counts, float *loss,
+                              void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Fused training on 16-bit features: the step, the Adam epochs and the L-BFGS

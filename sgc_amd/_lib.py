@@ -152,6 +152,13 @@ SIGNATURES = {
                                           _i64, _i32, ctypes.c_double, ctypes.c_double,
                                           ctypes.c_double, ctypes.c_double, ctypes.c_double, _p,
                                           _p, _i64, _p]),
+    "sgc_train_adam_sweep_workspace": (_i64, [_i64, _i64, _i64, _i64]),
+    "sgc_train_adam_sweep_f32": (ctypes.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _p,
+                                                _p, _p, _p, _i64, _i32, ctypes.c_double,
+                                                ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                                _p, _p, _p, _i64, _p]),
+    "sgc_linear_eval_sweep_f32": (ctypes.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _p,
+                                                 _p, _p, _p, _p, _i64, _p]),
     "sgc_linear_xent_x16_workspace": (_i64, [_i64, _i64, _i64]),
     "sgc_linear_xent_x16": (ctypes.c_int, [_p, _i32, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p,
                                            _p, _p, _i64, _p]),

@@ -36,6 +36,19 @@
 // launch 2 therefore reads the copy launch 1 made, never b itself.
 // X is read with 4-B loads only (any K, any ldx >= K, a 4-B aligned base), and
 // never past column K of a row.  No atomics; every sum has a fixed order.
+//
+//   sgc_train_adam_sweep_f32   B models on the same X and labels (the weight-
+//                        decay search of the reference's tuning.py): the two
+//                        launches above on a K-block x model grid
+//                        (adam_sweep_logits_kernel, adam_sweep_update_kernel).
+// Both pairs of kernels run the same __device__ bodies (small_logits_body,
+// small_update_body); the batched pair hands them model blockIdx.y's slices of
+// W, b and the moments, its own partial-logit area and bias copy in the
+// workspace, and its own decay, read from the device table.  A workgroup of
+// model i reads and writes model i's slices and area only, so the argument
+// above holds model by model: across models nothing is shared but X and the
+// labels, which no launch writes.  Each model's result is bit-identical to a
+// single-model call.
 #include <algorithm>
 #include <cmath>
 
@@ -49,6 +62,15 @@ namespace sgc {
 int g_adam_kernel = 0;
 // The schedule the last sgc_train_adam_f32 call ran (1 / 2; 0: none yet).
 int g_adam_kernel_last = 0;
+// What the last sgc_train_adam_sweep_f32 call ran: 2 the batched small
+// schedule, 1 the general schedule model by model, 0 none yet.
+int g_adam_sweep_last = 0;
+// sgc_set_tuning("adam_sweep_form"): the batched launch 2 -- 0 auto, 1 fused (one
+// launch), 2 split (softmax per model, then dW over K-block x model); and the
+// form the last batched call ran (1 / 2; 0: none yet).
+int g_adam_sweep_form = 0;
+int g_adam_sweep_form_last = 0;
+constexpr int kSweepMaxModels = 4096;
 
 AdamCoef adam_coef(int64_t step, double lr, double beta1, double beta2, double eps,
                    double weight_decay) {
@@ -144,14 +166,16 @@ __device__ __forceinline__ void load_x_tile(const float *__restrict__ X, int64_t
     }
 }
 
-__global__ __launch_bounds__(256) void adam_small_logits_kernel(
-    const float *__restrict__ X, int64_t ldx, const float *__restrict__ W,
+// Launch 1 of one model: K-block `blk` of the model whose W, b, P and bias copy
+// are given (the single-model kernel passes its arguments, the batched one
+// the slices of model blockIdx.y).
+__device__ __forceinline__ void small_logits_body(
+    const unsigned blk, const float *__restrict__ X, int64_t ldx, const float *__restrict__ W,
     const float *__restrict__ b, int M, int K, int C, int C16, float *__restrict__ P,
-    float *__restrict__ bias_copy) {
-    extern __shared__ __attribute__((aligned(16))) float lds1[];
+    float *__restrict__ bias_copy, float *lds1) {
     float *wt = lds1;                  // [64][C16]: W's block, transposed
     float *xs = lds1 + kSmallBK * C16;  // [M][65]
-    const int k0 = blockIdx.x * kSmallBK;
+    const int k0 = blk * kSmallBK;
     {
         const int k = threadIdx.x & 63;
         const bool ok = k0 + k < K;
@@ -165,13 +189,13 @@ __global__ __launch_bounds__(256) void adam_small_logits_kernel(
         }
     }
     load_x_tile(X, ldx, M, K, k0, xs, kSmallBK + 1);
-    if (blockIdx.x == 0 && (int)threadIdx.x < C16)
+    if (blk == 0 && (int)threadIdx.x < C16)
         bias_copy[threadIdx.x] = (b && (int)threadIdx.x < C) ? b[threadIdx.x] : 0.f;
     __syncthreads();
     // a task: row m, classes 4 c4 .. 4 c4 + 3
     typedef float f4 __attribute__((ext_vector_type(4)));
     const int q4 = C16 >> 2;
-    float *out = P + (int64_t)blockIdx.x * M * C16;
+    float *out = P + (int64_t)blk * M * C16;
     for (int o = threadIdx.x; o < M * q4; o += 256) {
         const int m = o / q4, c4 = o - m * q4;
         const float *xr = xs + m * (kSmallBK + 1);
@@ -187,22 +211,40 @@ __global__ __launch_bounds__(256) void adam_small_logits_kernel(
     }
 }
 
+__global__ __launch_bounds__(256) void adam_small_logits_kernel(
+    const float *__restrict__ X, int64_t ldx, const float *__restrict__ W,
+    const float *__restrict__ b, int M, int K, int C, int C16, float *__restrict__ P,
+    float *__restrict__ bias_copy) {
+    extern __shared__ __attribute__((aligned(16))) float lds1[];
+    small_logits_body(blockIdx.x, X, ldx, W, b, M, K, C, C16, P, bias_copy, lds1);
+}
+
+// The batched grid: K-block x model.  Model i = blockIdx.y owns W + i w_stride,
+// b + i C and the workspace area ws + i ws_stride floats (its bias copy, then
+// its partial logits at kSweepBias floats).
+constexpr int kSweepBias = 64;  // floats ahead of a model's P: its bias copy (256 B)
+__global__ __launch_bounds__(256) void adam_sweep_logits_kernel(
+    const float *__restrict__ X, int64_t ldx, const float *__restrict__ W,
+    const float *__restrict__ b, int M, int K, int C, int C16, float *__restrict__ ws,
+    int64_t w_stride, int64_t ws_stride) {
+    extern __shared__ __attribute__((aligned(16))) float sweep_lds1[];
+    const int64_t i = blockIdx.y;
+    float *area = ws + i * ws_stride;
+    small_logits_body(blockIdx.x, X, ldx, W + i * w_stride, b ? b + i * C : nullptr, M, K, C, C16,
+                      area + kSweepBias, area, sweep_lds1);
+}
+
+// Launch 2 of one model, in three parts that the batched split form runs in
+// two launches (a workgroup per model for the first and the last, then the
+// K-block x model grid for the second).
+// Part 1: z = partial logits summed over the blocks + bias, the row softmax,
+// G = (softmax - onehot) / M and the rows' loss terms, into gs [M][C16 + 1].
 template <int NT>
-__global__ __launch_bounds__(256) void adam_small_update_kernel(
-    const float *__restrict__ X, int64_t ldx, float *__restrict__ W, float *__restrict__ b,
-    const int64_t *__restrict__ labels, int M, int K, int C, int n_blk,
-    const float *__restrict__ P, const float *__restrict__ bias_copy, float inv_m, double inv_m_d,
-    float *__restrict__ mW, float *__restrict__ vW, float *__restrict__ mb, float *__restrict__ vb,
-    AdamCoef coef, float *__restrict__ loss_out) {
-    constexpr int C16 = NT * 16, LDG = C16 + 1, NQ = C16 / 4;
-    extern __shared__ __attribute__((aligned(16))) float lds2[];
-    double *lossp = reinterpret_cast<double *>(lds2);  // [1]
-    float *dbp = lds2 + 8;                              // [4][64]
-    float *gs = lds2 + kSmallScratch / 4;               // [M][LDG]
-    float *xs = gs + M * LDG;                           // [M][64]
+__device__ __forceinline__ void small_softmax_part(
+    const int64_t *__restrict__ labels, int M, int C, int n_blk, const float *__restrict__ P,
+    const float *__restrict__ bias_copy, float inv_m, float *gs) {
+    constexpr int C16 = NT * 16, LDG = C16 + 1;
     const int t = threadIdx.x;
-    const int k0 = blockIdx.x * kSmallBK;
-    load_x_tile(X, ldx, M, K, k0, xs, kSmallBK);
     // z = (sum of the partial logits, blocks ascending) + bias
     // (four elements per thread at a time, 16 blocks each: 64 loads in
     // flight; an element past M * C or a block past n_blk adds 0, after the
@@ -259,6 +301,16 @@ __global__ __launch_bounds__(256) void adam_small_update_kernel(
         z[C16] = (mx - zy) + ls;
     }
     __syncthreads();
+}
+
+// Part 2: dW of K-block k0 / 64 from gs and the X tile xs [M][64], then the
+// Adam update of that block of W.
+template <int NT>
+__device__ __forceinline__ void small_dw_part(
+    const int k0, float *__restrict__ W, float *__restrict__ mW, float *__restrict__ vW, int M,
+    int K, int C, const float *gs, const float *xs, const AdamCoef &coef) {
+    constexpr int C16 = NT * 16, LDG = C16 + 1, NQ = C16 / 4;
+    const int t = threadIdx.x;
     // dW[c][k0 + k] = sum_m G[m][c] X[m][k0 + k]: wave w owns classes w, w + 4, ...
     {
         const int w = __builtin_amdgcn_readfirstlane(t >> 6), k = t & 63;
@@ -288,7 +340,18 @@ __global__ __launch_bounds__(256) void adam_small_update_kernel(
             }
         }
     }
-    if (blockIdx.x != 0) return;  // (uniform per block)
+}
+
+// Part 3 (one workgroup per model): db from gs, the update of b, the loss.
+template <int NT>
+__device__ __forceinline__ void small_bias_part(
+    float *__restrict__ b, float *__restrict__ mb, float *__restrict__ vb, int M, int C,
+    const float *gs, float *scratch, double inv_m_d, const AdamCoef &coef,
+    float *__restrict__ loss_out) {
+    constexpr int C16 = NT * 16, LDG = C16 + 1;
+    double *lossp = reinterpret_cast<double *>(scratch);  // [1]
+    float *dbp = scratch + 8;                              // [4][64]
+    const int t = threadIdx.x;
     // db[c]: four interleaved partial sums over the rows, then in order
     {
         const int c = t & 63, part = t >> 6;
@@ -314,6 +377,114 @@ __global__ __launch_bounds__(256) void adam_small_update_kernel(
         mb[t] = m1;
         vb[t] = v1;
     }
+}
+
+// Launch 2 of one model: K-block `blk`; every pointer is the model's own.
+template <int NT>
+__device__ __forceinline__ void small_update_body(
+    const unsigned blk, const float *__restrict__ X, int64_t ldx, float *__restrict__ W,
+    float *__restrict__ b, const int64_t *__restrict__ labels, int M, int K, int C, int n_blk,
+    const float *__restrict__ P, const float *__restrict__ bias_copy, float inv_m, double inv_m_d,
+    float *__restrict__ mW, float *__restrict__ vW, float *__restrict__ mb, float *__restrict__ vb,
+    const AdamCoef &coef, float *__restrict__ loss_out, float *lds2) {
+    constexpr int C16 = NT * 16, LDG = C16 + 1;
+    float *gs = lds2 + kSmallScratch / 4;  // [M][LDG]
+    float *xs = gs + M * LDG;              // [M][64]
+    const int k0 = blk * kSmallBK;
+    load_x_tile(X, ldx, M, K, k0, xs, kSmallBK);
+    small_softmax_part<NT>(labels, M, C, n_blk, P, bias_copy, inv_m, gs);
+    small_dw_part<NT>(k0, W, mW, vW, M, K, C, gs, xs, coef);
+    if (blk != 0) return;  // (uniform per block)
+    small_bias_part<NT>(b, mb, vb, M, C, gs, lds2, inv_m_d, coef, loss_out);
+}
+
+template <int NT>
+__global__ __launch_bounds__(256) void adam_small_update_kernel(
+    const float *__restrict__ X, int64_t ldx, float *__restrict__ W, float *__restrict__ b,
+    const int64_t *__restrict__ labels, int M, int K, int C, int n_blk,
+    const float *__restrict__ P, const float *__restrict__ bias_copy, float inv_m, double inv_m_d,
+    float *__restrict__ mW, float *__restrict__ vW, float *__restrict__ mb, float *__restrict__ vb,
+    AdamCoef coef, float *__restrict__ loss_out) {
+    extern __shared__ __attribute__((aligned(16))) float lds2[];
+    small_update_body<NT>(blockIdx.x, X, ldx, W, b, labels, M, K, C, n_blk, P, bias_copy, inv_m,
+                          inv_m_d, mW, vW, mb, vb, coef, loss_out, lds2);
+}
+
+// Model i = blockIdx.y: its slices of W, b and the moments, its workspace area,
+// its decay wd[i] (one uniform load: the "wd == 0" skip of adam_update stays a
+// per-workgroup branch) and its loss slot loss_out[i * loss_stride].
+template <int NT>
+__global__ __launch_bounds__(256) void adam_sweep_update_kernel(
+    const float *__restrict__ X, int64_t ldx, float *__restrict__ W, float *__restrict__ b,
+    const int64_t *__restrict__ labels, int M, int K, int C, int n_blk,
+    const float *__restrict__ ws, float inv_m, double inv_m_d, float *__restrict__ mW,
+    float *__restrict__ vW, float *__restrict__ mb, float *__restrict__ vb, AdamCoef coef,
+    const float *__restrict__ wd, float *__restrict__ loss_out, int64_t w_stride,
+    int64_t ws_stride, int64_t loss_stride) {
+    extern __shared__ __attribute__((aligned(16))) float sweep_lds2[];
+    const int64_t i = blockIdx.y;
+    coef.wd = wd[i];
+    const float *area = ws + i * ws_stride;
+    const int64_t ow = i * w_stride, ob = i * C;
+    small_update_body<NT>(blockIdx.x, X, ldx, W + ow, b ? b + ob : nullptr, labels, M, K, C, n_blk,
+                          area + kSweepBias, area, inv_m, inv_m_d, mW + ow, vW + ow,
+                          b ? mb + ob : nullptr, b ? vb + ob : nullptr, coef,
+                          loss_out ? loss_out + i * loss_stride : nullptr, sweep_lds2);
+}
+
+// The split form of the batched launch 2.  In the form above every K-block's
+// workgroup re-sums all n_blk partial-logit blocks of its model and redoes the
+// softmax: B n_blk^2 M C16 4 bytes of L2 reads per epoch.  Here one workgroup
+// per model does that once (part 1), stores G [M][C16 + 1] to the model's
+// workspace area (g_off floats into it) and finishes the bias and the loss
+// (part 3); the K-block x model grid then loads G and its X tile and runs part
+// 2.  Same parts, same sums in the same orders: the same bits.
+template <int NT>
+__global__ __launch_bounds__(256) void adam_sweep_softmax_kernel(
+    float *__restrict__ b, const int64_t *__restrict__ labels, int M, int C, int n_blk,
+    float *__restrict__ ws, float inv_m, double inv_m_d, float *__restrict__ mb,
+    float *__restrict__ vb, AdamCoef coef, const float *__restrict__ wd,
+    float *__restrict__ loss_out, int64_t ws_stride, int64_t g_off, int64_t loss_stride) {
+    constexpr int LDG = NT * 16 + 1;
+    extern __shared__ __attribute__((aligned(16))) float sweep_lds3[];
+    float *gs = sweep_lds3 + kSmallScratch / 4;  // [M][LDG]
+    const int64_t i = blockIdx.x;
+    coef.wd = wd[i];
+    float *area = ws + i * ws_stride;
+    small_softmax_part<NT>(labels, M, C, n_blk, area + kSweepBias, area, inv_m, gs);
+    float *G = area + g_off;
+    for (int o = threadIdx.x; o < M * LDG; o += 256) G[o] = gs[o];
+    const int64_t ob = i * C;
+    small_bias_part<NT>(b ? b + ob : nullptr, b ? mb + ob : nullptr, b ? vb + ob : nullptr, M, C, gs,
+                        sweep_lds3, inv_m_d, coef,
+                        loss_out ? loss_out + i * loss_stride : nullptr);
+}
+
+template <int NT>
+__global__ __launch_bounds__(256) void adam_sweep_dw_kernel(
+    const float *__restrict__ X, int64_t ldx, float *__restrict__ W, int M, int K, int C,
+    const float *__restrict__ ws, float *__restrict__ mW, float *__restrict__ vW, AdamCoef coef,
+    const float *__restrict__ wd, int64_t w_stride, int64_t ws_stride, int64_t g_off) {
+    constexpr int LDG = NT * 16 + 1;
+    extern __shared__ __attribute__((aligned(16))) float sweep_lds4[];
+    float *gs = sweep_lds4;    // [M][LDG]
+    float *xs = gs + M * LDG;  // [M][64]
+    const int64_t i = blockIdx.y;
+    coef.wd = wd[i];
+    const int k0 = blockIdx.x * kSmallBK;
+    load_x_tile(X, ldx, M, K, k0, xs, kSmallBK);
+    const float *G = ws + i * ws_stride + g_off;
+    for (int o0 = threadIdx.x; o0 < M * LDG; o0 += 8 * 256) {  // (eight loads in flight)
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = o0 + 256 * u < M * LDG ? G[o0 + 256 * u] : 0.f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (o0 + 256 * u < M * LDG) gs[o0 + 256 * u] = v[u];
+    }
+    __syncthreads();
+    const int64_t ow = i * w_stride;
+    small_dw_part<NT>(k0, W + ow, mW + ow, vW + ow, M, K, C, gs, xs, coef);
 }
 
 bool small_eligible(int64_t M, int64_t K, int64_t C) {
@@ -345,6 +516,13 @@ int adam_set_tuning(int64_t value) {
     SGC_REQUIRE(value >= 0 && value <= 2, SGC_EINVAL,
                 "adam_kernel must be 0 (auto), 1 (general) or 2 (small)");
     g_adam_kernel = (int)value;
+    return SGC_OK;
+}
+
+int adam_sweep_set_form(int64_t value) {
+    SGC_REQUIRE(value >= 0 && value <= 2, SGC_EINVAL,
+                "adam_sweep_form must be 0 (auto), 1 (fused) or 2 (split)");
+    g_adam_sweep_form = (int)value;
     return SGC_OK;
 }
 
@@ -461,6 +639,162 @@ int train_adam(const float *X, int64_t ldx, float *W, float *b, const int64_t *l
         SGC_REQUIRE(err == hipSuccess, SGC_EHIP, "train_adam launch failed: %s",
                     hipGetErrorString(err));
     }
+    return SGC_OK;
+}
+
+// ---- the weight-decay sweep: B models on one X --------------------------------
+// Workspace of the batched small schedule: after the 256-B alignment slack,
+// one area per model -- its bias copy (256 B), its partial logits, then G
+// [M][C16 + 1] (written by the split form only).
+static int64_t sweep_area_bytes(int64_t M, int64_t K, int64_t C) {
+    const int64_t C16 = (C + 15) / 16 * 16, n_blk = (K + kSmallBK - 1) / kSmallBK;
+    return kSweepBias * 4 + al256(n_blk * M * C16 * 4) + al256(M * (C16 + 1) * 4);
+}
+// (floats from an area's start to its G: the split form's softmax - onehot)
+static int64_t sweep_g_offset(int64_t M, int64_t K, int64_t C) {
+    const int64_t C16 = (C + 15) / 16 * 16, n_blk = (K + kSmallBK - 1) / kSmallBK;
+    return (kSweepBias * 4 + al256(n_blk * M * C16 * 4)) / 4;
+}
+
+// The form of the batched launch 2 (see adam_sweep_softmax_kernel), from the
+// A/B of scripts/adam_sweep_ab.py (profiles/adam_sweep/ab.log).
+// The split form pays one more launch per epoch (2 - 3 us: slower at every
+// B = 1 and at 8 models of Pubmed's and Cora's shape) and saves the fused
+// form's redundant reads, B n_blk^2 M C16 4 bytes per epoch.  The largest
+// measured loss was at 38 MB of them (Cora, B = 8: 47.8 -> 49.3 us per epoch),
+// the smallest measured gain at 206 MB (Citeseer, B = 8: 60.4 -> 52.1 us;
+// 1.55 GB at Citeseer B = 60: 307 -> 158 us): split from 100 MB up.
+static bool sweep_split(int64_t B, int64_t M, int64_t K, int64_t C) {
+    if (g_adam_sweep_form) return g_adam_sweep_form == 2;
+    const int64_t C16 = (C + 15) / 16 * 16, n_blk = (K + kSmallBK - 1) / kSmallBK;
+    return B * n_blk * n_blk * M * C16 * 4 >= 100 * 1000 * 1000;
+}
+
+int64_t train_adam_sweep_workspace(int64_t B, int64_t M, int64_t K, int64_t C) {
+    if (B < 1 || B > kSweepMaxModels || M <= 0 || K <= 0 || C <= 0 || C > 64) return 0;
+    const int64_t batched = small_eligible(M, K, C) ? 256 + B * sweep_area_bytes(M, K, C) : 0;
+    return std::max(xent_workspace_bytes(M, K, C), batched);
+}
+
+// The batched small schedule wherever small_eligible holds and "adam_kernel" is
+// not 1: small_auto's crossover was measured for one model, whose two launches
+// leave most of the machine idle; nobody has measured where a batch crosses
+// over, so the sweep does not apply it.  Everything else -- M > kSmallMaxM,
+// "adam_kernel" = 1 -- runs the general schedule model by model.
+int train_adam_sweep(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels,
+                     int64_t B, int64_t M, int64_t K, int64_t C, float *mW, float *vW, float *mb,
+                     float *vb, int64_t step0, int32_t epochs, double lr, double beta1,
+                     double beta2, double eps, const float *wd_dev, float *loss_trace, void *ws,
+                     int64_t ws_bytes, hipStream_t s) {
+    SGC_REQUIRE(epochs >= 0, SGC_EINVAL, "train_adam_sweep: epochs=%d < 0", epochs);
+    SGC_REQUIRE(B >= 1 && B <= kSweepMaxModels, SGC_EINVAL, "train_adam_sweep: B=%lld outside 1..%d",
+                (long long)B, kSweepMaxModels);
+    SGC_REQUIRE(M > 0 && K > 0 && C > 0 && C <= 64 && ldx >= K, SGC_EINVAL,
+                "train_adam_sweep: bad shape M=%lld K=%lld C=%lld ldx=%lld (1 <= C <= 64, ldx >= K)",
+                (long long)M, (long long)K, (long long)C, (long long)ldx);
+    SGC_REQUIRE(step0 >= 0, SGC_EINVAL, "train_adam_sweep: step0=%lld < 0", (long long)step0);
+    SGC_REQUIRE(b ? (mb && vb) : (!mb && !vb), SGC_EINVAL,
+                "train_adam_sweep: b and its two moments must be given or NULL together");
+    SGC_REQUIRE(wd_dev, SGC_EINVAL, "train_adam_sweep: null weight_decay_dev");
+    SGC_REQUIRE(X && W && labels && mW && vW && ws, SGC_EINVAL, "train_adam_sweep: null pointer");
+    if (const int rc = xent_adam_check(M, K, C, ldx)) return rc;
+    const int64_t need = train_adam_sweep_workspace(B, M, K, C);
+    SGC_REQUIRE(ws_bytes >= need, SGC_ENOMEM, "train_adam_sweep: workspace %lld < %lld",
+                (long long)ws_bytes, (long long)need);
+    if (epochs == 0) return SGC_OK;
+    const bool batched = small_eligible(M, K, C) && g_adam_kernel != 1;
+    g_adam_sweep_last = batched ? 2 : 1;
+    const int64_t w_stride = C * K;
+    if (!batched) {
+        for (int64_t i = 0; i < B; ++i) {
+            const int64_t ow = i * w_stride, ob = i * C;
+            for (int e = 0; e < epochs; ++e) {
+                // (coef.wd is a placeholder: the last launch reads wd_dev[i])
+                const AdamCoef coef = adam_coef(step0 + e + 1, lr, beta1, beta2, eps, 0.0);
+                if (const int rc = xent_adam_epoch(
+                        X, ldx, W + ow, b ? b + ob : nullptr, labels, M, K, C, mW + ow, vW + ow,
+                        b ? mb + ob : nullptr, b ? vb + ob : nullptr, coef,
+                        loss_trace ? loss_trace + i * epochs + e : nullptr, ws, ws_bytes, s,
+                        wd_dev + i))
+                    return rc;
+            }
+        }
+        return SGC_OK;
+    }
+    const int NT = (int)((C + 15) / 16), C16 = NT * 16;
+    const int n_blk = (int)((K + kSmallBK - 1) / kSmallBK);
+    float *area0 = (float *)(((uintptr_t)ws + 255) & ~uintptr_t(255));
+    const int64_t ws_stride = sweep_area_bytes(M, K, C) / 4;
+    const size_t lds1 = (size_t)small_lds1(M, C16), lds2 = (size_t)small_lds2(M, C16);
+    const bool split = sweep_split(B, M, K, C);
+    g_adam_sweep_form_last = split ? 2 : 1;
+    int cus = 0;
+    SGC_HIP_CHECK(persistent_setup((const void *)adam_sweep_logits_kernel, &cus));
+#define SGC_ADAM_SWEEP_SETUP(N)                                                              \
+    do {                                                                                     \
+        SGC_HIP_CHECK(persistent_setup((const void *)adam_sweep_update_kernel<N>, &cus));    \
+        SGC_HIP_CHECK(persistent_setup((const void *)adam_sweep_softmax_kernel<N>, &cus));   \
+        SGC_HIP_CHECK(persistent_setup((const void *)adam_sweep_dw_kernel<N>, &cus));        \
+    } while (0)
+    switch (NT) {
+        case 1: SGC_ADAM_SWEEP_SETUP(1); break;
+        case 2: SGC_ADAM_SWEEP_SETUP(2); break;
+        case 3: SGC_ADAM_SWEEP_SETUP(3); break;
+        default: SGC_ADAM_SWEEP_SETUP(4); break;
+    }
+#undef SGC_ADAM_SWEEP_SETUP
+    const int64_t g_off = sweep_g_offset(M, K, C);
+    const size_t lds3 = (size_t)(kSmallScratch + M * (C16 + 1) * 4);
+    const size_t lds4 = (size_t)((M * (C16 + 1) + M * kSmallBK) * 4);
+    const float inv_m = 1.0f / (float)M;
+    const double inv_m_d = 1.0 / (double)M;
+    const dim3 grid((unsigned)n_blk, (unsigned)B);
+    for (int e = 0; e < epochs; ++e) {
+        const AdamCoef coef = adam_coef(step0 + e + 1, lr, beta1, beta2, eps, 0.0);
+        float *loss_out = loss_trace ? loss_trace + e : nullptr;
+        hipLaunchKernelGGL(adam_sweep_logits_kernel, grid, dim3(256), lds1, s, X, ldx, W, b, (int)M,
+                           (int)K, (int)C, C16, area0, w_stride, ws_stride);
+#define SGC_ADAM_SWEEP(N)                                                                          \
+    if (split) {                                                                                  \
+        hipLaunchKernelGGL(adam_sweep_softmax_kernel<N>, dim3((unsigned)B), dim3(256), lds3, s, b, \
+                           labels, (int)M, (int)C, n_blk, area0, inv_m, inv_m_d, mb, vb, coef,    \
+                           wd_dev, loss_out, ws_stride, g_off, (int64_t)epochs);                  \
+        hipLaunchKernelGGL(adam_sweep_dw_kernel<N>, grid, dim3(256), lds4, s, X, ldx, W, (int)M,  \
+                           (int)K, (int)C, area0, mW, vW, coef, wd_dev, w_stride, ws_stride,      \
+                           g_off);                                                                \
+    } else                                                                                        \
+        hipLaunchKernelGGL(adam_sweep_update_kernel<N>, grid, dim3(256), lds2, s, X, ldx, W, b,   \
+                           labels, (int)M, (int)K, (int)C, n_blk, area0, inv_m, inv_m_d, mW, vW,  \
+                           mb, vb, coef, wd_dev, loss_out, w_stride, ws_stride, (int64_t)epochs)
+        switch (NT) {
+            case 1: SGC_ADAM_SWEEP(1); break;
+            case 2: SGC_ADAM_SWEEP(2); break;
+            case 3: SGC_ADAM_SWEEP(3); break;
+            default: SGC_ADAM_SWEEP(4); break;
+        }
+#undef SGC_ADAM_SWEEP
+        const hipError_t err = hipGetLastError();
+        SGC_REQUIRE(err == hipSuccess, SGC_EHIP, "train_adam_sweep launch failed: %s",
+                    hipGetErrorString(err));
+    }
+    return SGC_OK;
+}
+
+// One host call, the existing launch chain once per model on the one
+// workspace: the stream orders model i + 1's chain behind model i's.
+int linear_eval_sweep_f32(const float *X, int64_t ldx, const float *W, const float *b,
+                          const int64_t *labels, int64_t B, int64_t M, int64_t K, int64_t C,
+                          int64_t *pred, int64_t *confusion, int64_t *counts, float *loss, void *ws,
+                          int64_t ws_bytes, hipStream_t s) {
+    SGC_REQUIRE(B >= 1 && B <= kSweepMaxModels, SGC_EINVAL,
+                "linear_eval_sweep: B=%lld outside 1..%d", (long long)B, kSweepMaxModels);
+    for (int64_t i = 0; i < B; ++i)
+        // (a bad argument fails model 0's call, before any launch)
+        if (const int rc = linear_eval_f32(
+                X, ldx, W ? W + i * C * K : nullptr, b ? b + i * C : nullptr, labels, M, K, C,
+                pred ? pred + i * M : nullptr, confusion ? confusion + i * C * C : nullptr,
+                counts ? counts + 2 * i : nullptr, loss ? loss + i : nullptr, ws, ws_bytes, s))
+            return rc;
     return SGC_OK;
 }
 

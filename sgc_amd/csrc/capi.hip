@@ -30,15 +30,19 @@ int sgc_abi_version(void) { return SGC_ABI_VERSION; }
 
 const char *sgc_last_error(void) { return g_err; }
 
-// ("adam_kernel" / "adam_kernel_last" belong to adam.hip; every other key to spmm.hip's table)
+// ("adam_kernel" / "adam_kernel_last" and the "adam_sweep_*" words belong to adam.hip; every other key to spmm.hip's table)
 int sgc_set_tuning(const char *key, int64_t value) {
     if (key && std::strcmp(key, "adam_kernel") == 0) return adam_set_tuning(value);
+    if (key && std::strcmp(key, "adam_sweep_form") == 0) return adam_sweep_set_form(value);
     return set_tuning(key, value);
 }
 
 int64_t sgc_get_tuning(const char *key) {
     if (key && std::strcmp(key, "adam_kernel") == 0) return g_adam_kernel;
     if (key && std::strcmp(key, "adam_kernel_last") == 0) return g_adam_kernel_last;
+    if (key && std::strcmp(key, "adam_sweep_last") == 0) return g_adam_sweep_last;
+    if (key && std::strcmp(key, "adam_sweep_form") == 0) return g_adam_sweep_form;
+    if (key && std::strcmp(key, "adam_sweep_form_last") == 0) return g_adam_sweep_form_last;
     if (key && std::strcmp(key, "adam_small_max_rows") == 0) return adam_small_max_rows();
     return get_tuning(key);
 }
@@ -662,6 +666,30 @@ int sgc_linear_xent_x16(const void *X, int32_t x_dtype, int64_t ldx, const float
                         float *dW, float *db, void *ws, int64_t ws_bytes, void *stream) {
     return linear_xent_x16(X, x_dtype, ldx, W, b, labels, M, K, C, loss, dW, db, ws, ws_bytes,
                            as_stream(stream));
+}
+
+int64_t sgc_train_adam_sweep_workspace(int64_t B, int64_t M, int64_t K, int64_t C) {
+    return train_adam_sweep_workspace(B, M, K, C);
+}
+
+int sgc_train_adam_sweep_f32(const float *X, int64_t ldx, float *W, float *b,
+                             const int64_t *labels, int64_t B, int64_t M, int64_t K, int64_t C,
+                             float *exp_avg_W, float *exp_avg_sq_W, float *exp_avg_b,
+                             float *exp_avg_sq_b, int64_t step0, int32_t epochs, double lr,
+                             double beta1, double beta2, double eps, const float *weight_decay_dev,
+                             float *loss_trace, void *workspace, int64_t workspace_bytes,
+                             void *stream) {
+    return train_adam_sweep(X, ldx, W, b, labels, B, M, K, C, exp_avg_W, exp_avg_sq_W, exp_avg_b,
+                            exp_avg_sq_b, step0, epochs, lr, beta1, beta2, eps, weight_decay_dev,
+                            loss_trace, workspace, workspace_bytes, as_stream(stream));
+}
+
+int sgc_linear_eval_sweep_f32(const float *X, int64_t ldx, const float *W, const float *b,
+                              const int64_t *labels, int64_t B, int64_t M, int64_t K, int64_t C,
+                              int64_t *pred, int64_t *confusion, int64_t *counts, float *loss,
+                              void *workspace, int64_t workspace_bytes, void *stream) {
+    return linear_eval_sweep_f32(X, ldx, W, b, labels, B, M, K, C, pred, confusion, counts, loss,
+                                 workspace, workspace_bytes, as_stream(stream));
 }
 
 const char *sgc_linear_xent_x16_kernel_name(int64_t M, int64_t K, int64_t ldx, int64_t C,

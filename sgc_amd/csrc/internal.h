@@ -61,7 +61,8 @@ extern int g_linear_ck;
 // Classifier weight backward: 0 auto, 1 fp32 MFMA slabs, 2 split-bf16 slabs (xent.hip).
 extern int g_backward_kernel;
 extern int g_x16_vec, g_x16_step;              // spmm16.hip
-extern int g_adam_kernel, g_adam_kernel_last;  // adam.hip
+extern int g_adam_kernel, g_adam_kernel_last, g_adam_sweep_last;  // adam.hip
+extern int g_adam_sweep_form, g_adam_sweep_form_last;
 
 // sort.hip -- the library's own stable radix sort.
 // Bytes of device workspace radix_sort_pairs needs for n pairs.
@@ -108,12 +109,14 @@ int xent_closure(const int64_t *stop, const float *X, int64_t ldx, const float *
                  float *db, void *ws, hipStream_t s);
 // xent.hip: one epoch of the general schedule (launches A and B of the fused
 // classifier step, then the reduce + Adam kernel).  Arguments as
-// sgc_train_adam_f32; ws as linear_xent_f32's.
+// sgc_train_adam_f32; ws as linear_xent_f32's.  wd_dev non-null: the weight
+// decay is the device float *wd_dev (read by the last launch) and coef.wd is
+// ignored -- sgc_train_adam_sweep_f32's per-model decays.
 struct AdamCoef;  // adam_update.h
 int xent_adam_epoch(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels,
                     int64_t M, int64_t K, int64_t C, float *mW, float *vW, float *mb, float *vb,
                     const AdamCoef &coef, float *loss_out, void *ws, int64_t ws_bytes,
-                    hipStream_t s);
+                    hipStream_t s, const float *wd_dev = nullptr);
 int xent_adam_check(int64_t M, int64_t K, int64_t C, int64_t ldx);
 
 int coo_to_csr_workspace(int64_t n_rows, int64_t nnz, size_t *bytes);
@@ -292,6 +295,7 @@ int train_lbfgs(const float *X, int64_t ldx, float *W, float *b, const int64_t *
                 int32_t max_eval, double tol_grad, double tol_change, float *loss_trace,
                 int64_t *status_trace, void *ws, int64_t ws_bytes, hipStream_t s);
 int adam_set_tuning(int64_t value);
+int adam_sweep_set_form(int64_t value);
 int64_t adam_small_max_rows();
 int adam_step(int32_t n_tensors, float *const *params, const float *const *grads,
               float *const *exp_avgs, float *const *exp_avg_sqs, const int64_t *numels,
@@ -302,6 +306,16 @@ int train_adam(const float *X, int64_t ldx, float *W, float *b, const int64_t *l
                int64_t K, int64_t C, float *mW, float *vW, float *mb, float *vb, int64_t step0,
                int32_t epochs, double lr, double beta1, double beta2, double eps,
                double weight_decay, float *loss_trace, void *ws, int64_t ws_bytes, hipStream_t s);
+int64_t train_adam_sweep_workspace(int64_t B, int64_t M, int64_t K, int64_t C);
+int train_adam_sweep(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels,
+                     int64_t B, int64_t M, int64_t K, int64_t C, float *mW, float *vW, float *mb,
+                     float *vb, int64_t step0, int32_t epochs, double lr, double beta1,
+                     double beta2, double eps, const float *wd_dev, float *loss_trace, void *ws,
+                     int64_t ws_bytes, hipStream_t s);
+int linear_eval_sweep_f32(const float *X, int64_t ldx, const float *W, const float *b,
+                          const int64_t *labels, int64_t B, int64_t M, int64_t K, int64_t C,
+                          int64_t *pred, int64_t *confusion, int64_t *counts, float *loss, void *ws,
+                          int64_t ws_bytes, hipStream_t s);
 
 
 }  // namespace sgc

@@ -764,11 +764,11 @@ __global__ __launch_bounds__(256) void xent_reduce_small_kernel(
 // order, then W / exp_avg / exp_avg_sq in place; blocks dw_blocks + c (c < C):
 // db[c] in xent_reduce_small_kernel's order, then b[c] (skipped when b is
 // null); block dw_blocks + C: the loss, to *loss_out when non-null.
-__global__ __launch_bounds__(256) void xent_reduce_adam_kernel(
+__device__ __forceinline__ void xent_reduce_adam_body(
     const float *__restrict__ slab, int n_slabs, int C, int K, int C16, int dw_blocks,
     const double *__restrict__ loss_part, const float *__restrict__ db_part, int n_waves,
     double inv_m, float *__restrict__ W, float *__restrict__ mW, float *__restrict__ vW,
-    float *__restrict__ b, float *__restrict__ mb, float *__restrict__ vb, AdamCoef coef,
+    float *__restrict__ b, float *__restrict__ mb, float *__restrict__ vb, const AdamCoef &coef,
     float *__restrict__ loss_out) {
     __shared__ float part[4][64];
     if ((int)blockIdx.x < dw_blocks) {
@@ -802,6 +802,30 @@ __global__ __launch_bounds__(256) void xent_reduce_adam_kernel(
             vb[c] = v;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void xent_reduce_adam_kernel(
+    const float *__restrict__ slab, int n_slabs, int C, int K, int C16, int dw_blocks,
+    const double *__restrict__ loss_part, const float *__restrict__ db_part, int n_waves,
+    double inv_m, float *__restrict__ W, float *__restrict__ mW, float *__restrict__ vW,
+    float *__restrict__ b, float *__restrict__ mb, float *__restrict__ vb, AdamCoef coef,
+    float *__restrict__ loss_out) {
+    xent_reduce_adam_body(slab, n_slabs, C, K, C16, dw_blocks, loss_part, db_part, n_waves, inv_m,
+                          W, mW, vW, b, mb, vb, coef, loss_out);
+}
+
+// The same launch with the weight decay read from device memory (one uniform
+// load): sgc_train_adam_sweep_f32's general schedule, whose decays live on the
+// device and are never read back by the host.
+__global__ __launch_bounds__(256) void xent_reduce_adam_wd_kernel(
+    const float *__restrict__ slab, int n_slabs, int C, int K, int C16, int dw_blocks,
+    const double *__restrict__ loss_part, const float *__restrict__ db_part, int n_waves,
+    double inv_m, float *__restrict__ W, float *__restrict__ mW, float *__restrict__ vW,
+    float *__restrict__ b, float *__restrict__ mb, float *__restrict__ vb, AdamCoef coef,
+    const float *__restrict__ wd, float *__restrict__ loss_out) {
+    coef.wd = *wd;
+    xent_reduce_adam_body(slab, n_slabs, C, K, C16, dw_blocks, loss_part, db_part, n_waves, inv_m,
+                          W, mW, vW, b, mb, vb, coef, loss_out);
 }
 
 // The launchers: run-time V (tile_vec) and NT (class tiles) through
@@ -1069,7 +1093,7 @@ int xent_adam_check(int64_t M, int64_t K, int64_t C, int64_t ldx) {
 int xent_adam_epoch(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels,
                     int64_t M, int64_t K, int64_t C, float *mW, float *vW, float *mb, float *vb,
                     const AdamCoef &coef, float *loss_out, void *ws, int64_t ws_bytes,
-                    hipStream_t s) {
+                    hipStream_t s, const float *wd_dev) {
     const int64_t need = xent_workspace_bytes(M, K, C);
     SGC_REQUIRE(ws_bytes >= need, SGC_ENOMEM, "train_adam: workspace %lld < %lld",
                 (long long)ws_bytes, (long long)need);
@@ -1077,10 +1101,16 @@ int xent_adam_epoch(const float *X, int64_t ldx, float *W, float *b, const int64
     if (const int rc = xent_launch_ab(nullptr, X, ldx, W, b, labels, M, K, C, nullptr, 0, ws, s, part))
         return rc;
     const int dw_blocks = (int)((C * K + 63) / 64);
-    hipLaunchKernelGGL(xent_reduce_adam_kernel, dim3((unsigned)(dw_blocks + C + 1)), dim3(256), 0,
-                       s, part.slab, part.n_parts, (int)C, (int)K, part.C16, dw_blocks,
-                       part.loss_part, part.db_part, part.waves, 1.0 / (double)M, W, mW, vW, b, mb,
-                       vb, coef, loss_out);
+    if (wd_dev)  // (coef.wd is replaced by *wd_dev on the device)
+        hipLaunchKernelGGL(xent_reduce_adam_wd_kernel, dim3((unsigned)(dw_blocks + C + 1)),
+                           dim3(256), 0, s, part.slab, part.n_parts, (int)C, (int)K, part.C16,
+                           dw_blocks, part.loss_part, part.db_part, part.waves, 1.0 / (double)M, W,
+                           mW, vW, b, mb, vb, coef, wd_dev, loss_out);
+    else
+        hipLaunchKernelGGL(xent_reduce_adam_kernel, dim3((unsigned)(dw_blocks + C + 1)), dim3(256),
+                           0, s, part.slab, part.n_parts, (int)C, (int)K, part.C16, dw_blocks,
+                           part.loss_part, part.db_part, part.waves, 1.0 / (double)M, W, mW, vW, b,
+                           mb, vb, coef, loss_out);
     SGC_HIP_CHECK(hipGetLastError());
     return SGC_OK;
 }

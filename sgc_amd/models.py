@@ -187,6 +187,18 @@ def _check_labels(labels, C, ignore_index):
     _checked_labels[key] = (weakref.ref(labels, lambda r, key=key: _forget_labels(r, key)), state)
 
 
+def _check_eval_labels(labels, C):
+    """SGC.evaluate's label check (tuning.ModelBank.evaluate shares it): no
+    label is skipped, one outside [0, C) raises IndexError."""
+    try:
+        # (_check_labels excuses labels equal to its ignore_index: class 0 lies in
+        # range, so as "ignore_index" it excuses no out-of-range label)
+        _check_labels(labels, C, 0)
+    except IndexError as e:
+        raise IndexError(f"{str(e).split(' (')[0]} (classes: {C}; SGC.evaluate skips no "
+                         "label, ignore_index is not supported)") from None
+
+
 def _cross_entropy_args(args, kwargs):
     """(logits, labels, ignore_index) when F.cross_entropy(*args, **kwargs) is
     the plain form the HIP kernels compute (mean reduction, no class weights,
@@ -288,14 +300,7 @@ class SGC(nn.Module):
         from .metrics import Evaluation
         if labels.dim() != 1 or labels.shape[0] != x.shape[0]:
             raise RuntimeError("SGC.evaluate: one label per row expected")
-        C = self.W.weight.shape[0]
-        try:
-            # (_check_labels excuses labels equal to its ignore_index: class 0 lies in
-            # range, so as "ignore_index" it excuses no out-of-range label)
-            _check_labels(labels, C, 0)
-        except IndexError as e:
-            raise IndexError(f"{str(e).split(' (')[0]} (classes: {C}; SGC.evaluate skips no "
-                             "label, ignore_index is not supported)") from None
+        _check_eval_labels(labels, self.W.weight.shape[0])
         ev = _linear_eval(x, self.W.weight, self.W.bias, labels)
         return Evaluation(ev.confusion, ev.counts[0], ev.counts[1], ev.loss, len(labels))
 
