@@ -804,6 +804,84 @@ int sgc_train_lbfgs_f32(const float *X, int64_t ldx, float *W, float *b, const i
                         void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Wide L-BFGS: sgc_lbfgs_iterate_f32's contract for 1 <= n < 2^31 - 1
+ * parameters (memory permitting), history_size 1..1024, spread over the
+ * machine.  The two-loop recursion runs in coefficient space: the state keeps,
+ * in fp64, every dot product between the basis vectors {s_i, y_i, g} (the Gram
+ * block), and d is formed as one linear combination of the basis.  One
+ * iteration is six launches whatever n and hist_len are; no host
+ * synchronisation, no allocation, no atomics.  Status words, stop reasons, the
+ * stop word's meaning, the NaN branches and the arithmetic contract (fp32
+ * vectors, fp64 accumulation of exact products in a fixed order that depends
+ * on n only, single-fmaf updates) are the narrow call's.  Results are bitwise
+ * reproducible and tolerance-equal to torch and to the narrow call (the
+ * recursion's intermediate q and r are never rounded to fp32 here).
+ *
+ *   sgc_lbfgs_wide_workspace(n, history_size): bytes of the state (0 and an
+ *     sgc_last_error text when the shape is refused).  Layout, m =
+ *     history_size, ld = n rounded up to 32 floats; the f32 rows are 128-B
+ *     aligned (ld * 4 is a multiple of 128), every other block 256-B aligned
+ *     and padded to a multiple of 256 B:
+ *       header 256 B   the narrow header (the six status words, head, n,
+ *                      history_size, ld, loss, prev_loss, H_diag, t), then the
+ *                      hand-over words of the six launches
+ *       ro[m] f32      1 / ys per ring slot
+ *       d[ld], prev_g[ld], S[m][ld], Y[m][ld]   f32 rows, pad columns zero
+ *       s_new[ld], y_new[ld]   the staged pair t d and g - prev_g: it enters
+ *                      the ring only once accepted (ys > 1e-10), so a rejected
+ *                      pair never touches the slot it would evict
+ *       coef[2m+1] f64 the direction's coefficients, logical order (s, y, g)
+ *       red[16+6m] f64 the summed dots of the last scan
+ *       G[2m+1][2m+1] f64   the Gram block: index k < m is S slot k, m + k is
+ *                      Y slot k, 2m is g (after an iteration: prev_g)
+ *       partials[ceil(ld / tile)][16+6m] f64   per-workgroup partial dots;
+ *                      tile = 1024 floats up to ld = 262,144, 2048 up to
+ *                      1,048,576, 4096 above
+ *   sgc_lbfgs_wide_init / _begin_step / _iterate_f32 / _read_status: arguments
+ *     and errors as the narrow four, without the 65,536 limit.  The library
+ *     remembers (address -> n, history_size) from init until init is called
+ *     on that address again: a freed and reused address must be initialised
+ *     anew before any other call, as for the narrow state.
+ *   sgc_lbfgs_wide_sync_gram: recomputes every Gram entry from the rows as they
+ *     lie in the state (prev_g as g), with the dot routine and order of the
+ *     incremental path.  For a state whose rows the caller wrote (a state
+ *     loaded from elsewhere); a state the iterations built never needs it.
+ *   sgc_lbfgs_wide_l2_f32: the reference's L2 term (TextSGC train.py) on one
+ *     tensor behind the state's stop word: grad += l2 W (one fmaf each) and
+ *     *loss += (float)(0.5 l2 sum W^2), the sum in fp64 partials of 4096
+ *     elements in order.  l2 == 0 enqueues nothing.  numel <= the state's n;
+ *     uses the state's partials block, so it goes between the closure and
+ *     sgc_lbfgs_wide_iterate_f32.
+ *   sgc_train_lbfgs_wide_f32: sgc_train_lbfgs_f32's loop on the wide iteration:
+ *     per step the reset, max_iter times [the closure of sgc_linear_xent_f32
+ *     behind the stop word (C <= 64, its 31-bit offset limits), the L2 term on
+ *     W (never on b) when l2 != 0, the iteration on [W] (b NULL) or [W, b]],
+ *     the status snapshot.  loss_trace / status_trace as the narrow call.
+ *     Bit-identical to the same steps driven call by call.
+ * Argument errors return SGC_EINVAL / SGC_ERANGE / SGC_ENOMEM with an
+ * sgc_last_error text before any device call.
+ * ------------------------------------------------------------------------- */
+int64_t sgc_lbfgs_wide_workspace(int64_t n, int32_t history_size);
+int sgc_lbfgs_wide_init(void *state, int64_t state_bytes, int64_t n, int32_t history_size,
+                        void *stream);
+int sgc_lbfgs_wide_begin_step(void *state, void *stream);
+int sgc_lbfgs_wide_iterate_f32(void *state, int32_t n_tensors, float *const *param_ptrs_host,
+                               const float *const *grad_ptrs_host, const int64_t *numels_host,
+                               const float *loss, double lr, int32_t max_iter, int32_t max_eval,
+                               double tolerance_grad, double tolerance_change, void *stream);
+int sgc_lbfgs_wide_read_status(const void *state, int64_t *out_host, void *stream);
+int sgc_lbfgs_wide_sync_gram(void *state, void *stream);
+int sgc_lbfgs_wide_l2_f32(void *state, const float *W, float *grad, int64_t numel, double l2,
+                          float *loss, void *stream);
+int64_t sgc_train_lbfgs_wide_workspace(int64_t M, int64_t K, int64_t C);
+int sgc_train_lbfgs_wide_f32(const float *X, int64_t ldx, float *W, float *b,
+                             const int64_t *labels, int64_t M, int64_t K, int64_t C, void *state,
+                             int32_t steps, double lr, int32_t max_iter, int32_t max_eval,
+                             double tolerance_grad, double tolerance_change, double l2,
+                             float *loss_trace, int64_t *status_trace, void *workspace,
+                             int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Device-resident Adam: optim.Adam of citation.py:41-50 (torch's default
  * single-tensor math: amsgrad=False, maximize=False, coupled L2 weight decay).
  *

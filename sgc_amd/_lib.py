@@ -144,6 +144,19 @@ SIGNATURES = {
     "sgc_train_lbfgs_f32": (ctypes.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _i32,
                                            ctypes.c_double, _i32, _i32, ctypes.c_double,
                                            ctypes.c_double, _p, _p, _p, _i64, _p]),
+    "sgc_lbfgs_wide_workspace": (_i64, [_i64, _i32]),
+    "sgc_lbfgs_wide_init": (ctypes.c_int, [_p, _i64, _i64, _i32, _p]),
+    "sgc_lbfgs_wide_begin_step": (ctypes.c_int, [_p, _p]),
+    "sgc_lbfgs_wide_iterate_f32": (ctypes.c_int, [_p, _i32, _p, _p, _p, _p, ctypes.c_double, _i32,
+                                                  _i32, ctypes.c_double, ctypes.c_double, _p]),
+    "sgc_lbfgs_wide_read_status": (ctypes.c_int, [_p, ctypes.POINTER(_i64), _p]),
+    "sgc_lbfgs_wide_sync_gram": (ctypes.c_int, [_p, _p]),
+    "sgc_lbfgs_wide_l2_f32": (ctypes.c_int, [_p, _p, _p, _i64, ctypes.c_double, _p, _p]),
+    "sgc_train_lbfgs_wide_workspace": (_i64, [_i64, _i64, _i64]),
+    "sgc_train_lbfgs_wide_f32": (ctypes.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _i32,
+                                                ctypes.c_double, _i32, _i32, ctypes.c_double,
+                                                ctypes.c_double, ctypes.c_double, _p, _p, _p,
+                                                _i64, _p]),
     "sgc_adam_step_f32": (ctypes.c_int, [_i32, _p, _p, _p, _p, _p, _i64, ctypes.c_double,
                                          ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                          ctypes.c_double, _p]),

@@ -15,7 +15,8 @@ LIB = os.path.join(HERE, "libsgc_amd.so")
 SOURCES = ["capi.hip", "spmm.hip", "ingest.hip", "linear.hip", "normalize.hip", "xent.hip",
            "subgraph.hip", "cpu.hip", "mgpu.hip", "plan.hip", "groups.hip", "sort.hip",
            "exchange.hip", "loss.hip", "spmm16.hip", "lbfgs.hip", "linear16.hip", "adam.hip",
-           "xent_fwd_stop.hip", "xent16.hip", "eval.hip", "eval16.hip"]
+           "xent_fwd_stop.hip", "xent16.hip", "eval.hip", "eval16.hip",
+           "lbfgs_wide.hip"]
 
 
 def _headers():

@@ -712,6 +712,56 @@ int sgc_train_adam_x16(const void *X, int32_t x_dtype, int64_t ldx, float *W, fl
                           weight_decay, loss_trace, workspace, workspace_bytes, as_stream(stream));
 }
 
+int64_t sgc_lbfgs_wide_workspace(int64_t n, int32_t history_size) {
+    return lbfgs_wide_workspace(n, history_size);
+}
+
+int sgc_lbfgs_wide_init(void *state, int64_t state_bytes, int64_t n, int32_t history_size,
+                        void *stream) {
+    return lbfgs_wide_init(state, state_bytes, n, history_size, as_stream(stream));
+}
+
+int sgc_lbfgs_wide_begin_step(void *state, void *stream) {
+    return lbfgs_wide_begin_step(state, as_stream(stream));
+}
+
+int sgc_lbfgs_wide_iterate_f32(void *state, int32_t n_tensors, float *const *param_ptrs_host,
+                               const float *const *grad_ptrs_host, const int64_t *numels_host,
+                               const float *loss, double lr, int32_t max_iter, int32_t max_eval,
+                               double tolerance_grad, double tolerance_change, void *stream) {
+    return lbfgs_wide_iterate(state, n_tensors, param_ptrs_host, grad_ptrs_host, numels_host, loss,
+                              lr, max_iter, max_eval, tolerance_grad, tolerance_change,
+                              as_stream(stream));
+}
+
+int sgc_lbfgs_wide_read_status(const void *state, int64_t *out_host, void *stream) {
+    return lbfgs_wide_read_status(state, out_host, as_stream(stream));
+}
+
+int sgc_lbfgs_wide_sync_gram(void *state, void *stream) {
+    return lbfgs_wide_sync_gram(state, as_stream(stream));
+}
+
+int sgc_lbfgs_wide_l2_f32(void *state, const float *W, float *grad, int64_t numel, double l2,
+                          float *loss, void *stream) {
+    return lbfgs_wide_l2(state, W, grad, numel, l2, loss, as_stream(stream));
+}
+
+int64_t sgc_train_lbfgs_wide_workspace(int64_t M, int64_t K, int64_t C) {
+    return train_lbfgs_wide_workspace(M, K, C);
+}
+
+int sgc_train_lbfgs_wide_f32(const float *X, int64_t ldx, float *W, float *b,
+                             const int64_t *labels, int64_t M, int64_t K, int64_t C, void *state,
+                             int32_t steps, double lr, int32_t max_iter, int32_t max_eval,
+                             double tolerance_grad, double tolerance_change, double l2,
+                             float *loss_trace, int64_t *status_trace, void *workspace,
+                             int64_t workspace_bytes, void *stream) {
+    return train_lbfgs_wide(X, ldx, W, b, labels, M, K, C, state, steps, lr, max_iter, max_eval,
+                            tolerance_grad, tolerance_change, l2, loss_trace, status_trace,
+                            workspace, workspace_bytes, as_stream(stream));
+}
+
 int64_t sgc_train_lbfgs_x16_workspace(int64_t M, int64_t K, int64_t C) {
     return train_lbfgs_x16_workspace(M, K, C);
 }
@@ -779,6 +829,7 @@ int sgc_warmup(uint32_t units, void *stream) {
         SGC_HIP_CHECK(warm_xent_fwd_stop(s));
         SGC_HIP_CHECK(warm_loss(s));
         SGC_HIP_CHECK(warm_lbfgs(s));
+        SGC_HIP_CHECK(warm_lbfgs_wide(s));
         SGC_HIP_CHECK(warm_adam(s));
     }
     if (units & SGC_WARM_LOADERS) {

@@ -294,6 +294,25 @@ int train_lbfgs(const float *X, int64_t ldx, float *W, float *b, const int64_t *
                 int64_t K, int64_t C, void *state, int32_t steps, double lr, int32_t max_iter,
                 int32_t max_eval, double tol_grad, double tol_change, float *loss_trace,
                 int64_t *status_trace, void *ws, int64_t ws_bytes, hipStream_t s);
+// lbfgs_wide.hip: the iteration in Gram form over the whole machine
+hipError_t warm_lbfgs_wide(hipStream_t);
+int64_t lbfgs_wide_workspace(int64_t n, int32_t history_size);
+int lbfgs_wide_init(void *state, int64_t bytes, int64_t n, int32_t history_size, hipStream_t s);
+int lbfgs_wide_begin_step(void *state, hipStream_t s);
+int lbfgs_wide_iterate(void *state, int32_t n_tensors, float *const *params,
+                       const float *const *grads, const int64_t *numels, const float *loss,
+                       double lr, int32_t max_iter, int32_t max_eval, double tol_grad,
+                       double tol_change, hipStream_t s);
+int lbfgs_wide_read_status(const void *state, int64_t *out_host, hipStream_t s);
+int lbfgs_wide_sync_gram(void *state, hipStream_t s);
+int lbfgs_wide_l2(void *state, const float *W, float *gW, int64_t numel, double l2, float *loss,
+                  hipStream_t s);
+int64_t train_lbfgs_wide_workspace(int64_t M, int64_t K, int64_t C);
+int train_lbfgs_wide(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels,
+                     int64_t M, int64_t K, int64_t C, void *state, int32_t steps, double lr,
+                     int32_t max_iter, int32_t max_eval, double tol_grad, double tol_change,
+                     double l2, float *loss_trace, int64_t *status_trace, void *ws,
+                     int64_t ws_bytes, hipStream_t s);
 int adam_set_tuning(int64_t value);
 int adam_sweep_set_form(int64_t value);
 int64_t adam_small_max_rows();

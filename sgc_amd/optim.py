@@ -40,6 +40,14 @@ path driven with the closure `sgc_cross_entropy(model, x, y).backward()`
 (float32 features) or with `propagate.linear_xent(x, W, b, y)` assigning
 .grad (16-bit features).
 
+LBFGS(..., wide=True) lifts the 65,536-element limit: above it step() drives
+sgc_lbfgs_wide_iterate_f32, the same iteration in Gram form spread over the
+machine (csrc/lbfgs_wide.hip, six launches per iteration whatever the sizes);
+at or below it the narrow kernel runs as before, bit for bit.  run_steps then
+also takes TextSGC's training (sgc_amd.textsgc: a model without a bias, the
+L2 term `l2`); see the method.  The default, wide=False, is the class as it
+was.
+
 Results of the device path are tolerance-equal to torch's (fp64-accumulated
 dot products in a fixed order; torch sums in fp32) and bitwise reproducible
 run to run.  state_dict() does not carry the device state.
@@ -61,6 +69,8 @@ from . import _lib
 from .propagate import X16_DTYPES, is_x16, xent_x16_layout
 
 MAX_NUMEL = 65536
+WIDE_MAX_NUMEL = 2 ** 31 - 1  # LBFGS(wide=True): sgc_lbfgs_wide_iterate_f32's limit
+_SGC_ERANGE = 2  # include/sgc_amd.h
 MAX_TENSORS = 16
 MAX_HISTORY = 1024
 
@@ -68,11 +78,12 @@ STOP_NONE, STOP_OPT_AT_ENTRY, STOP_MAX_ITER, STOP_MAX_EVAL, STOP_OPT, STOP_GTD, 
     STOP_STEP_SMALL, STOP_LOSS_CHANGE = range(8)
 
 
-def _read_status(lib, state, stream):
+def _read_status(lib, state, stream, wide=False):
     """(n_iter, func_evals, iters, evals, stop, hist_len): the one host
     synchronisation of a step."""
     out = (ctypes.c_int64 * 6)()
-    _lib.check(lib.sgc_lbfgs_read_status(_lib.ptr(state), out, stream), "lbfgs_read_status")
+    read = lib.sgc_lbfgs_wide_read_status if wide else lib.sgc_lbfgs_read_status
+    _lib.check(read(_lib.ptr(state), out, stream), "lbfgs_read_status")
     return tuple(out)
 
 
@@ -82,7 +93,17 @@ def _read_status_trace(table):
     return [tuple(row) for row in table.cpu().view(-1, 6).tolist()]
 
 
-class LBFGS(torch.optim.LBFGS):
+class _WideOption(type(torch.optim.LBFGS)):
+    """LBFGS(..., wide=False): the keyword is taken off before __init__, whose
+    signature stays torch's plus poll_every."""
+
+    def __call__(cls, *args, wide=False, **kwargs):
+        opt = super().__call__(*args, **kwargs)
+        opt.wide = bool(wide)
+        return opt
+
+
+class LBFGS(torch.optim.LBFGS, metaclass=_WideOption):
     def __init__(self, params, lr=1, max_iter=20, max_eval=None, tolerance_grad=1e-7,
                  tolerance_change=1e-9, history_size=100, line_search_fn=None, poll_every=None):
         super().__init__(params, lr=lr, max_iter=max_iter, max_eval=max_eval,
@@ -91,6 +112,8 @@ class LBFGS(torch.optim.LBFGS):
         if poll_every is not None and int(poll_every) < 1:
             raise ValueError(f"poll_every must be None or >= 1, got {poll_every}")
         self.poll_every = None if poll_every is None else int(poll_every)
+        self.wide = False       # LBFGS(..., wide=True): see the module docstring
+        self._dev_wide = False  # the device state is sgc_lbfgs_wide_workspace's
         self._dev_state = None  # uint8 device tensor (sgc_lbfgs_workspace bytes)
         self._dev_key = None    # (parameter identities and shapes, history_size) it was built for
         self.last_status = None  # (n_iter, func_evals, iters, evals, stop, hist_len) of the last step
@@ -110,7 +133,8 @@ class LBFGS(torch.optim.LBFGS):
         for p in ps:
             if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
                 return False
-        return 1 <= sum(p.numel() for p in ps) <= MAX_NUMEL
+        n = sum(p.numel() for p in ps)
+        return 1 <= n <= MAX_NUMEL or (self.wide and MAX_NUMEL < n < WIDE_MAX_NUMEL)
 
     def _key(self):
         return (tuple((id(p), p.numel()) for p in self._params),
@@ -130,12 +154,18 @@ class LBFGS(torch.optim.LBFGS):
         closure = torch.enable_grad()(closure)
         with torch.cuda.device(dev):
             stream = _lib.stream_handle(dev)
-            state = self._ensure_state(lib, dev, stream)
+            wide = self._dev_wide if self._dev_state is not None else \
+                sum(p.numel() for p in ps) > MAX_NUMEL
+            state = self._ensure_state(lib, dev, stream, wide)
+            begin_step = lib.sgc_lbfgs_wide_begin_step if wide else lib.sgc_lbfgs_begin_step
+            iterate = lib.sgc_lbfgs_wide_iterate_f32 if wide else lib.sgc_lbfgs_iterate_f32
+            read = (lambda: _read_status(lib, state, stream, True)) if wide else \
+                (lambda: _read_status(lib, state, stream))
             nt = len(ps)
             p_ptrs = (ctypes.c_void_p * nt)(*[p.data_ptr() for p in ps])
             numels = (ctypes.c_int64 * nt)(*[p.numel() for p in ps])
             lr = float(group["lr"])
-            _lib.check(lib.sgc_lbfgs_begin_step(_lib.ptr(state), stream), "lbfgs_begin_step")
+            _lib.check(begin_step(_lib.ptr(state), stream), "lbfgs_begin_step")
             orig_loss = None
             status = None
             for it in range(group["max_iter"]):
@@ -146,58 +176,75 @@ class LBFGS(torch.optim.LBFGS):
                 grads = [self._dense_grad(p) for p in ps]  # kept alive until the launch is queued
                 g_ptrs = (ctypes.c_void_p * nt)(*[None if g is None else g.data_ptr()
                                                   for g in grads])
-                _lib.check(lib.sgc_lbfgs_iterate_f32(
+                _lib.check(iterate(
                     _lib.ptr(state), nt, p_ptrs, g_ptrs, numels, _lib.ptr(dloss), lr,
                     group["max_iter"], group["max_eval"], float(group["tolerance_grad"]),
                     float(group["tolerance_change"]), stream), "lbfgs_iterate_f32")
                 if self.poll_every and (it + 1) % self.poll_every == 0 and \
                         it + 1 < group["max_iter"]:
-                    status = _read_status(lib, state, stream)
+                    status = read()
                     if status[4] != STOP_NONE:
                         break
                     status = None
             if status is None:
-                status = _read_status(lib, state, stream)
+                status = read()
         self.last_status = status
         st = self.state[ps[0]]
         st["n_iter"], st["func_evals"] = int(status[0]), int(status[1])
         return orig_loss
 
-    def _ensure_state(self, lib, dev, stream):
-        """The device state, built (and zeroed) on first use."""
+    def _ensure_state(self, lib, dev, stream, wide=False):
+        """The device state, built (and zeroed) on first use: the narrow
+        kernel's, or with `wide` sgc_lbfgs_wide_workspace's."""
         if self._dev_state is None:
             group = self.param_groups[0]
             n = sum(p.numel() for p in self._params)
-            nbytes = lib.sgc_lbfgs_workspace(n, group["history_size"])
+            workspace = lib.sgc_lbfgs_wide_workspace if wide else lib.sgc_lbfgs_workspace
+            init = lib.sgc_lbfgs_wide_init if wide else lib.sgc_lbfgs_init
+            nbytes = workspace(n, group["history_size"])
             if nbytes <= 0:
                 _lib.check(1, "lbfgs_workspace")
             state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.sgc_lbfgs_init(_lib.ptr(state), nbytes, n, group["history_size"],
-                                          stream), "lbfgs_init")
-            self._dev_state, self._dev_key = state, self._key()
+            _lib.check(init(_lib.ptr(state), nbytes, n, group["history_size"], stream),
+                       "lbfgs_init")
+            self._dev_state, self._dev_key, self._dev_wide = state, self._key(), bool(wide)
+        elif self._dev_wide != bool(wide):
+            raise ValueError("sgc_amd.optim.LBFGS: the device state was built by the %s kernel; "
+                             "one optimiser cannot alternate between the two" %
+                             ("wide" if self._dev_wide else "narrow"))
         return self._dev_state
 
     # -- whole steps in one host call ---------------------------------------------------
-    def _fused_plan(self, model, features, labels):
+    def _fused_plan(self, model, features, labels, wide=False):
         """(W, b, x) when run_steps can run as one sgc_train_lbfgs_f32 /
         sgc_train_lbfgs_x16 call on x (the features in the layout the call
-        takes)."""
+        takes).  With `wide` (and wide=True at construction) the plan of one
+        sgc_train_lbfgs_wide_f32 call instead: the model may also be an
+        sgc_amd.textsgc.SGC, the bias may be missing (b is None) and the
+        features are float32."""
         from .models import SGC
-        if type(model) is not SGC or model.W.bias is None or not self.device_path():
+        kinds = (SGC,)
+        if wide:
+            from .textsgc import SGC as TextSGC
+            kinds = (SGC, TextSGC)
+        if (wide and not self.wide) or type(model) not in kinds or not self.device_path():
             return None
         W, b = model.W.weight, model.W.bias
+        if b is None and not wide:
+            return None
         ps = self._params
-        if len(ps) != 2 or ps[0] is not W or ps[1] is not b:
+        if len(ps) != (1 if b is None else 2) or ps[0] is not W or (b is not None and
+                                                                    ps[1] is not b):
             return None
         x, y = features, labels
         if not (isinstance(x, torch.Tensor) and x.device == W.device and
-                (x.dtype == torch.float32 or is_x16(x)) and x.dim() == 2 and x.shape[0] >= 1 and
-                x.shape[1] == W.shape[1] and 1 <= W.shape[0] <= 64):
+                (x.dtype == torch.float32 or (is_x16(x) and not wide)) and x.dim() == 2 and
+                x.shape[0] >= 1 and x.shape[1] == W.shape[1] and 1 <= W.shape[0] <= 64):
             return None
         if not (isinstance(y, torch.Tensor) and y.dtype == torch.int64 and y.device == x.device and
                 y.shape == (x.shape[0],)):
             return None
-        if not (W.requires_grad and b.requires_grad):
+        if not (W.requires_grad and (b is None or b.requires_grad)):
             return None
         x = x.detach()
         if is_x16(x):
@@ -211,7 +258,51 @@ class LBFGS(torch.optim.LBFGS):
             return None
         return W, b, x
 
-    def run_steps(self, model, features, labels, steps):
+    def _run_steps_wide(self, plan, labels, steps, l2):
+        """run_steps' fused path on sgc_train_lbfgs_wide_f32; None (no device
+        state built, no launch) when the shape is past
+        the fused closure's 31-bit offset limits, which the call reports as
+        SGC_ERANGE from its argument checks: the literal loop runs then."""
+        if self._dev_state is not None and self._key() != self._dev_key:
+            raise ValueError("sgc_amd.optim.LBFGS: the parameter list or history_size changed "
+                             "after the first step")
+        W, b, x = plan
+        self.zero_grad(set_to_none=True)
+        group = self.param_groups[0]
+        y = labels.contiguous()
+        M, K = x.shape
+        C = W.shape[0]
+        dev = x.device
+        lib = _lib.load()
+        ws_bytes = lib.sgc_train_lbfgs_wide_workspace(M, K, C)
+        ws = getattr(self, "_train_ws", None)
+        if ws is None or ws.numel() < ws_bytes or ws.device != dev:
+            ws = self._train_ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=dev)
+        losses = torch.empty(steps, dtype=torch.float32, device=dev)
+        table = torch.empty(steps * 6, dtype=torch.int64, device=dev)
+        with torch.no_grad(), torch.cuda.device(dev):
+            stream = _lib.stream_handle(dev)
+
+            def call(state, n_steps):
+                return lib.sgc_train_lbfgs_wide_f32(
+                    _lib.ptr(x), x.stride(0), _lib.ptr(W), None if b is None else _lib.ptr(b),
+                    _lib.ptr(y), M, K, C, _lib.ptr(state), n_steps, float(group["lr"]),
+                    group["max_iter"], group["max_eval"], float(group["tolerance_grad"]),
+                    float(group["tolerance_change"]), float(l2), _lib.ptr(losses),
+                    _lib.ptr(table), _lib.ptr(ws), ws.numel(), stream)
+            # the argument checks alone (steps = 0 returns after them, before
+            # the state is looked at): a shape the closure refuses has no plan
+            if ws_bytes <= 0 or call(ws, 0) == _SGC_ERANGE:
+                return None
+            state = self._ensure_state(lib, dev, stream, True)
+            _lib.check(call(state, steps), "train_lbfgs_wide_f32")
+            self.step_statuses = _read_status_trace(table)
+        self.last_status = self.step_statuses[-1]
+        st = self.state[self._params[0]]
+        st["n_iter"], st["func_evals"] = int(self.last_status[0]), int(self.last_status[1])
+        return losses
+
+    def run_steps(self, model, features, labels, steps, l2=0.0):
         """`steps` times self.step(closure) with the reference closure --
         zero_grad, F.cross_entropy(model(features), labels), backward
         (reddit.py:51-64).  Returns the [steps] tensor of each step's first
@@ -226,18 +317,40 @@ class LBFGS(torch.optim.LBFGS):
         one read-back of the status table, the call's only synchronisation
         after the labels' one range check; the parameters' .grad is left None.
         Everything else runs the literal loop.  A label outside [0, C) other
-        than -100 raises IndexError on either path."""
+        than -100 raises IndexError on either path.
+
+        `l2` adds TextSGC's term 0.5 * l2 * (model.W.weight ** 2).sum() to the
+        closure (reference downstream/TextSGC/train.py:65-71; never on the
+        bias).  With wide=True the fused path also covers a model without a
+        bias, sgc_amd.textsgc.SGC, any parameter count and l2 != 0, all as one
+        sgc_train_lbfgs_wide_f32 call on float32 features; a model the narrow
+        call covers keeps the narrow call (and its bits) while l2 == 0.
+        A shape past the fused closure's 31-bit offset limits (the call's
+        SGC_ERANGE) and, without wide=True, l2 != 0 run the literal loop."""
         steps = int(steps)
         if steps < 0:
             raise ValueError(f"steps must be >= 0, got {steps}")
         if steps == 0:
             return None
-        plan = self._fused_plan(model, features, labels)
+        l2 = float(l2)
+        plan = None
+        if l2 == 0.0 and not (self._dev_state is not None and self._dev_wide) and \
+                sum(p.numel() for p in self._params) <= MAX_NUMEL:
+            plan = self._fused_plan(model, features, labels)
+        if plan is None and not (self._dev_state is not None and not self._dev_wide):
+            wide_plan = self._fused_plan(model, features, labels, wide=True)
+            if wide_plan is not None:
+                model.train()
+                losses = self._run_steps_wide(wide_plan, labels, steps, l2)
+                if losses is not None:
+                    return losses
         model.train()
         if plan is None:
             def closure():
                 self.zero_grad()
                 loss = F.cross_entropy(model(features), labels)
+                if l2 != 0.0:
+                    loss = loss + 0.5 * l2 * (model.W.weight ** 2).sum()
                 loss.backward()
                 return loss
             losses, self.step_statuses = [], []
