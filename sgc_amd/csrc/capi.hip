@@ -604,7 +604,7 @@ int sgc_lbfgs_init(void *state, int64_t state_bytes, int64_t n, int32_t history_
 }
 
 int sgc_lbfgs_begin_step(void *state, void *stream) {
-    return lbfgs_begin_step(state, as_stream(stream));
+    return lbfgs_begin_step("lbfgs_begin_step", state, as_stream(stream));
 }
 
 int sgc_lbfgs_iterate_f32(void *state, int32_t n_tensors, float *const *param_ptrs_host,
@@ -616,7 +616,7 @@ int sgc_lbfgs_iterate_f32(void *state, int32_t n_tensors, float *const *param_pt
 }
 
 int sgc_lbfgs_read_status(const void *state, int64_t *out_host, void *stream) {
-    return lbfgs_read_status(state, out_host, as_stream(stream));
+    return lbfgs_read_status("lbfgs_read_status", state, out_host, as_stream(stream));
 }
 
 int64_t sgc_train_lbfgs_workspace(int64_t M, int64_t K, int64_t C) {
@@ -722,7 +722,7 @@ int sgc_lbfgs_wide_init(void *state, int64_t state_bytes, int64_t n, int32_t his
 }
 
 int sgc_lbfgs_wide_begin_step(void *state, void *stream) {
-    return lbfgs_wide_begin_step(state, as_stream(stream));
+    return lbfgs_begin_step("lbfgs_wide_begin_step", state, as_stream(stream));
 }
 
 int sgc_lbfgs_wide_iterate_f32(void *state, int32_t n_tensors, float *const *param_ptrs_host,
@@ -735,7 +735,7 @@ int sgc_lbfgs_wide_iterate_f32(void *state, int32_t n_tensors, float *const *par
 }
 
 int sgc_lbfgs_wide_read_status(const void *state, int64_t *out_host, void *stream) {
-    return lbfgs_wide_read_status(state, out_host, as_stream(stream));
+    return lbfgs_read_status("lbfgs_wide_read_status", state, out_host, as_stream(stream));
 }
 
 int sgc_lbfgs_wide_sync_gram(void *state, void *stream) {

@@ -284,11 +284,12 @@ int mgpu_propagate(int64_t handle, const float *X, int64_t ldx, float *Y, int64_
                    int32_t K, hipStream_t stream);
 int64_t lbfgs_workspace(int64_t n, int32_t history_size);
 int lbfgs_init(void *state, int64_t bytes, int64_t n, int32_t history_size, hipStream_t s);
-int lbfgs_begin_step(void *state, hipStream_t s);
+// (begin_step and read_status serve both engines' states; `what` names the entry)
+int lbfgs_begin_step(const char *what, void *state, hipStream_t s);
 int lbfgs_iterate(void *state, int32_t n_tensors, float *const *params, const float *const *grads,
                   const int64_t *numels, const float *loss, double lr, int32_t max_iter,
                   int32_t max_eval, double tol_grad, double tol_change, hipStream_t s);
-int lbfgs_read_status(const void *state, int64_t *out_host, hipStream_t s);
+int lbfgs_read_status(const char *what, const void *state, int64_t *out_host, hipStream_t s);
 int64_t train_lbfgs_workspace(int64_t M, int64_t K, int64_t C);
 int train_lbfgs(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels, int64_t M,
                 int64_t K, int64_t C, void *state, int32_t steps, double lr, int32_t max_iter,
@@ -298,12 +299,10 @@ int train_lbfgs(const float *X, int64_t ldx, float *W, float *b, const int64_t *
 hipError_t warm_lbfgs_wide(hipStream_t);
 int64_t lbfgs_wide_workspace(int64_t n, int32_t history_size);
 int lbfgs_wide_init(void *state, int64_t bytes, int64_t n, int32_t history_size, hipStream_t s);
-int lbfgs_wide_begin_step(void *state, hipStream_t s);
 int lbfgs_wide_iterate(void *state, int32_t n_tensors, float *const *params,
                        const float *const *grads, const int64_t *numels, const float *loss,
                        double lr, int32_t max_iter, int32_t max_eval, double tol_grad,
                        double tol_change, hipStream_t s);
-int lbfgs_wide_read_status(const void *state, int64_t *out_host, hipStream_t s);
 int lbfgs_wide_sync_gram(void *state, hipStream_t s);
 int lbfgs_wide_l2(void *state, const float *W, float *gW, int64_t numel, double l2, float *loss,
                   hipStream_t s);

@@ -15,7 +15,7 @@
 //              of s_new, y_new and g against every ring row and one another,
 //              and of max|g|, |g|_1, max|t d|
 //   2 coef     (one workgroup) sums the partials in workgroup order, runs
-//              torch's entry tests, accepts the pair if ys > 1e-10, updates
+//              torch's entry tests, accepts or rejects the pair, updates
 //              the Gram block, H_diag and the step size, runs the two loops
 //              on coefficients
 //   3 direct   (n / tile) moves an accepted pair into its ring slot, writes
@@ -30,12 +30,14 @@
 // element order, a xor butterfly in the wave, the four waves in order, the
 // workgroup partials in workgroup order); coefficient-space sums in fp64;
 // x += t d a single fmaf.  The cut of [0, n) into tiles depends on n only.
+//
+// The header prefix, the tensor table, torch's decisions (entry tests, pair
+// acceptance), the state registry, init / begin / status and the fused
+// training loop are lbfgs_common.h's, shared with lbfgs.hip; this file holds
+// the six launches, the Gram maintenance, sync_gram and the L2 term.
 #include <cmath>
-#include <map>
-#include <mutex>
 
-#include "common.h"
-#include "internal.h"
+#include "lbfgs_common.h"
 
 namespace sgc {
 
@@ -43,42 +45,23 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / kWave;
-constexpr int kMaxTensors = 16;
-constexpr int kMaxHistory = 1024;
-constexpr int64_t kHeaderBytes = 256;
+constexpr const Engine &kE = kWideEngine;
 constexpr int kScalars = 16;  // leading dots of a partial block (9 used)
 constexpr int kBatch = 128;   // ring rows reduced per LDS image
 
 // partial / reduced dot slots
 enum { D_GMAX = 0, D_G1, D_TDMAX, D_SS, D_SY, D_YY, D_SG, D_YG, D_GG };
 
-// The first 104 bytes are lbfgs.hip's header (the six status words first).
-struct Header {
-    int64_t n_iter, func_evals, iters, evals, stop, hist_len;
-    int64_t head;
-    int64_t n, history_size, ld;
-    double loss, prev_loss;
-    float H_diag, t;
+struct Header : HeaderBase {
     int64_t live;       // coef -> direct, decide: this iteration passed the entry tests
     int64_t move;       // decide -> update: g.d passed; settle clears it
     int64_t pushed;     // coef -> direct: the staged pair goes into push_slot
     int64_t push_slot;
     int64_t nwg;        // tiles of the vector (tiles(ld): by n alone)
 };
-static_assert(sizeof(Header) <= kHeaderBytes, "header block");
+static_assert(sizeof(Header) == 144, "the wide words follow the shared prefix");
 
-struct Tensors {
-    float *p[kMaxTensors];
-    const float *g[kMaxTensors];
-    int64_t off[kMaxTensors + 1];
-    int32_t count;
-};
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-__host__ __device__ constexpr int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-__host__ __device__ constexpr int64_t row_ld(int64_t n) { return round_up(n, 32); }
-__host__ __device__ constexpr int64_t scalars_bytes(int64_t m) { return round_up(m * 4, 256); }
+typedef Tensors<int64_t> Table;
 
 // 16-B chunks per thread of a tile (tile = 1024 nv floats): by n alone
 __host__ __device__ constexpr int tile_nv(int64_t ld) {
@@ -112,10 +95,6 @@ __host__ __device__ inline Layout layout(int64_t n, int64_t m) {
     return L;
 }
 
-__device__ __forceinline__ double nan_max(double a, double b) {
-    return a != a ? a : (b != b ? b : (a > b ? a : b));
-}
-
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
@@ -127,23 +106,8 @@ __device__ __forceinline__ double wave_max(double v) {
     return v;
 }
 
-__device__ __forceinline__ f4 load_chunk(const float *row, int64_t nc, int64_t c) {
-    return c < nc ? reinterpret_cast<const f4 *>(row)[c] : f4{0.f, 0.f, 0.f, 0.f};
-}
-
-// element j of the flat gradient (NULL tensor: zeros, as torch substitutes)
-__device__ __forceinline__ float flat_grad(const Tensors &T, int64_t j) {
-    float v = 0.0f;
-    for (int ti = 0; ti < T.count; ++ti)
-        if (j >= T.off[ti] && j < T.off[ti + 1]) {
-            const float *gp = T.g[ti];
-            if (gp) v = gp[j - T.off[ti]];
-        }
-    return v;
-}
-
 template <int NV>
-__device__ __forceinline__ void load_grad(const Tensors &T, int64_t n, int64_t nc, int64_t c0,
+__device__ __forceinline__ void load_grad(const Table &T, int64_t n, int64_t nc, int64_t c0,
                                           f4 (&g)[NV]) {
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
@@ -200,7 +164,7 @@ __device__ __forceinline__ int ring_slot(int head, int i, int m) { return (head 
 
 // ---- 1 scan ---------------------------------------------------------------------
 template <int NV>
-__global__ __launch_bounds__(kThreads) void wide_scan_kernel(char *state, Tensors T) {
+__global__ __launch_bounds__(kThreads) void wide_scan_kernel(char *state, Table T) {
     __shared__ double red[kBatch][3][kWaves];
     __shared__ double sred[9][kWaves];
     const Header *H = reinterpret_cast<const Header *>(state);
@@ -318,14 +282,7 @@ __global__ __launch_bounds__(kThreads) void wide_coef_kernel(char *state,
     int stop = 0;
     func_evals += 1;
     evals += 1;
-    if (evals == 1) {
-        if (gmax <= tol_grad) stop = SGC_LBFGS_STOP_OPT_AT_ENTRY;
-    } else {
-        if (evals >= max_eval) stop = SGC_LBFGS_STOP_MAX_EVAL;
-        else if (gmax <= tol_grad) stop = SGC_LBFGS_STOP_OPT;
-        else if (red[D_TDMAX] <= tol_change) stop = SGC_LBFGS_STOP_STEP_SMALL;
-        else if (fabs(loss - prev_loss) < tol_change) stop = SGC_LBFGS_STOP_LOSS_CHANGE;
-    }
+    stop = entry_stop(evals, max_eval, gmax, red[D_TDMAX], loss, prev_loss, tol_grad, tol_change);
     if (stop != 0) {
         if (tid == 0) {
             H->func_evals = func_evals;
@@ -339,21 +296,13 @@ __global__ __launch_bounds__(kThreads) void wide_coef_kernel(char *state,
     iters += 1;
     const float g1 = (float)red[D_G1], ys = (float)red[D_SY], yy = (float)red[D_YY];
     const bool first = n_iter == 1;
-    const bool push = !first && (double)ys > 1e-10;
-    const bool evict = push && h == m;
-    int slot = 0;
-    if (push) {
-        if (evict) {
-            slot = head;
-            head = (head + 1) % m;
-        } else {
-            slot = (head + h) % m;
-            h += 1;
-        }
-        H_diag = ys / yy;
-    }
-    if (first) H_diag = 1.0f;
-    const float t = first ? ((1.0f / g1 < 1.0f) ? 1.0f / g1 : 1.0f) * lr : lr;
+    const PairDecision D = accept_pair(first, ys, yy, m, head, h, H_diag, [](int) {});
+    const bool push = D.push, evict = D.evict;
+    const int slot = D.slot;
+    head = D.head;
+    h = D.hist_len;
+    H_diag = D.H_diag;
+    const float t = step_size(first, g1, lr);
 
     // the Gram block: the pair's row and column (when accepted) and g's
     const int64_t ig = 2 * m;
@@ -443,7 +392,7 @@ __global__ __launch_bounds__(kThreads) void wide_coef_kernel(char *state,
 
 // ---- 3 direct -------------------------------------------------------------------
 template <int NV>
-__global__ __launch_bounds__(kThreads) void wide_direct_kernel(char *state, Tensors T) {
+__global__ __launch_bounds__(kThreads) void wide_direct_kernel(char *state, Table T) {
     __shared__ double c_s[2 * kMaxHistory + 1];
     __shared__ double wred[kWaves];
     const Header *H = reinterpret_cast<const Header *>(state);
@@ -543,7 +492,7 @@ __global__ void wide_settle_kernel(Header *H) {
 
 // ---- 5 update -------------------------------------------------------------------
 template <int NV>
-__global__ __launch_bounds__(kThreads) void wide_update_kernel(const char *state, Tensors T) {
+__global__ __launch_bounds__(kThreads) void wide_update_kernel(const char *state, Table T) {
     const Header *H = reinterpret_cast<const Header *>(state);
     if (H->move == 0) return;
     const int64_t n = H->n, nc = H->ld >> 2;
@@ -560,11 +509,7 @@ __global__ __launch_bounds__(kThreads) void wide_update_kernel(const char *state
         for (int e = 0; e < 4; ++e) {
             const int64_t j = 4 * c + e;
             if (j >= n) continue;
-            for (int ti = 0; ti < T.count; ++ti)
-                if (j >= T.off[ti] && j < T.off[ti + 1]) {
-                    float *pp = T.p[ti] + (j - T.off[ti]);
-                    *pp = fmaf(t, d[e], *pp);
-                }
+            update_param(T, j, t, d, e);
         }
     }
 }
@@ -648,39 +593,6 @@ __global__ void wide_l2_loss_kernel(const int64_t *stop, const double *part, int
     *loss = *loss + (float)(0.5 * l2 * a);
 }
 
-__global__ void wide_init_kernel(Header *H, int64_t n, int64_t m, int64_t ld, int64_t nwg) {
-    H->n = n;
-    H->history_size = m;
-    H->ld = ld;
-    H->H_diag = 1.0f;
-    H->nwg = nwg;
-}
-
-__global__ void wide_begin_kernel(Header *H) {
-    H->iters = 0;
-    H->evals = 0;
-    H->stop = 0;
-}
-
-__global__ void wide_snapshot_kernel(const Header *H, int64_t *out) {
-    out[0] = H->n_iter;
-    out[1] = H->func_evals;
-    out[2] = H->iters;
-    out[3] = H->evals;
-    out[4] = H->stop;
-    out[5] = H->hist_len;
-}
-
-// What sgc_lbfgs_wide_init recorded of each state, for the argument checks of
-// the later calls.  As in lbfgs.hip an entry lives until init is called on the
-// same address again: a caller that frees a state and reuses the address must
-// initialise it anew, which replaces the entry.
-struct Shape {
-    int64_t n, m;
-};
-std::mutex g_states_mu;
-std::map<const void *, Shape> g_states;
-
 #define WIDE_LAUNCH_NV(kernel, nv, grid, s, ...)                                              \
     do {                                                                                      \
         if ((nv) == 1) hipLaunchKernelGGL(kernel<1>, grid, dim3(kThreads), 0, s, __VA_ARGS__); \
@@ -690,7 +602,7 @@ std::map<const void *, Shape> g_states;
     } while (0)
 
 // the six launches of one iteration
-hipError_t enqueue_iterate(char *st, const Tensors &T, int64_t n, const float *loss, float lrf,
+hipError_t enqueue_iterate(char *st, const Table &T, int64_t n, const float *loss, float lrf,
                            int max_iter, int max_eval, double tol_grad, double tol_change,
                            hipStream_t s) {
     const int64_t ld = row_ld(n);
@@ -706,37 +618,10 @@ hipError_t enqueue_iterate(char *st, const Tensors &T, int64_t n, const float *l
     return hipGetLastError();
 }
 
-int check_shape(const char *what, int64_t n, int64_t history_size) {
-    SGC_REQUIRE(n >= 1, SGC_EINVAL, "%s: n=%lld < 1", what, (long long)n);
-    SGC_REQUIRE(n < INT32_MAX, SGC_ERANGE, "%s: n=%lld >= 2^31 - 1 parameters", what,
-                (long long)n);
-    SGC_REQUIRE(history_size >= 1, SGC_EINVAL, "%s: history_size=%lld < 1", what,
-                (long long)history_size);
-    SGC_REQUIRE(history_size <= kMaxHistory, SGC_ERANGE, "%s: history_size=%lld > %d", what,
-                (long long)history_size, kMaxHistory);
-    return SGC_OK;
-}
-
-int find_state(const char *what, const void *state, Shape &out) {
-    std::lock_guard<std::mutex> lock(g_states_mu);
-    auto it = g_states.find(state);
-    SGC_REQUIRE(it != g_states.end(), SGC_EINVAL,
-                "%s: state not initialised by sgc_lbfgs_wide_init", what);
-    out = it->second;
-    return SGC_OK;
-}
-
-void clear_tensors(Tensors &T) {
-    for (int i = 0; i < kMaxTensors; ++i) {
-        T.p[i] = nullptr;
-        T.g[i] = nullptr;
-    }
-}
-
 // the two launches of the L2 term (partials: the state's partial region, which
 // holds at least one double per 1024 floats of the vector)
-hipError_t enqueue_l2(char *st, const Shape &sh, const float *W, float *gW, int64_t ck, double l2,
-                      float *loss, hipStream_t s) {
+hipError_t enqueue_l2(char *st, const StateShape &sh, const float *W, float *gW, int64_t ck,
+                      double l2, float *loss, hipStream_t s) {
     const int64_t *stop = &reinterpret_cast<const Header *>(st)->stop;
     double *part = reinterpret_cast<double *>(st + layout(sh.n, sh.m).part);
     const int64_t nt = (ck + kL2Tile - 1) / kL2Tile;
@@ -750,89 +635,30 @@ hipError_t enqueue_l2(char *st, const Shape &sh, const float *W, float *gW, int6
 }  // namespace
 
 int64_t lbfgs_wide_workspace(int64_t n, int32_t history_size) {
-    if (check_shape("lbfgs_wide_workspace", n, history_size)) return 0;
+    if (check_shape("lbfgs_wide_workspace", n, history_size, kE)) return 0;
     return layout(n, history_size).bytes;
 }
 
 int lbfgs_wide_init(void *state, int64_t bytes, int64_t n, int32_t history_size, hipStream_t s) {
     SGC_REQUIRE(state, SGC_EINVAL, "lbfgs_wide_init: null state");
-    if (const int rc = check_shape("lbfgs_wide_init", n, history_size)) return rc;
-    const int64_t need = layout(n, history_size).bytes;
-    SGC_REQUIRE(bytes >= need, SGC_ENOMEM, "lbfgs_wide_init: state %lld < %lld bytes",
-                (long long)bytes, (long long)need);
-    SGC_REQUIRE(reinterpret_cast<uintptr_t>(state) % 256 == 0, SGC_EINVAL,
-                "lbfgs_wide_init: state not 256-B aligned");
-    SGC_HIP_CHECK(hipMemsetAsync(state, 0, (size_t)need, s));
-    const int64_t ld = row_ld(n);
-    hipLaunchKernelGGL(wide_init_kernel, dim3(1), dim3(1), 0, s, reinterpret_cast<Header *>(state),
-                       n, (int64_t)history_size, ld, tiles(ld));
-    SGC_HIP_CHECK(hipGetLastError());
-    std::lock_guard<std::mutex> lock(g_states_mu);
-    g_states[state] = Shape{n, history_size};
-    return SGC_OK;
-}
-
-int lbfgs_wide_begin_step(void *state, hipStream_t s) {
-    SGC_REQUIRE(state, SGC_EINVAL, "lbfgs_wide_begin_step: null state");
-    hipLaunchKernelGGL(wide_begin_kernel, dim3(1), dim3(1), 0, s,
-                       reinterpret_cast<Header *>(state));
-    SGC_HIP_CHECK(hipGetLastError());
-    return SGC_OK;
+    if (const int rc = check_shape("lbfgs_wide_init", n, history_size, kE)) return rc;
+    return state_init("lbfgs_wide_init", kE, state, bytes, layout(n, history_size).bytes, n,
+                      history_size, &reinterpret_cast<Header *>(state)->nwg, tiles(row_ld(n)), s);
 }
 
 int lbfgs_wide_iterate(void *state, int32_t n_tensors, float *const *params,
                        const float *const *grads, const int64_t *numels, const float *loss,
                        double lr, int32_t max_iter, int32_t max_eval, double tol_grad,
                        double tol_change, hipStream_t s) {
-    SGC_REQUIRE(state, SGC_EINVAL, "lbfgs_wide_iterate: null state");
-    SGC_REQUIRE(n_tensors >= 1 && n_tensors <= kMaxTensors, SGC_EINVAL,
-                "lbfgs_wide_iterate: n_tensors=%d outside 1..%d", n_tensors, kMaxTensors);
-    SGC_REQUIRE(params && grads && numels, SGC_EINVAL, "lbfgs_wide_iterate: null pointer table");
-    SGC_REQUIRE(max_iter >= 1, SGC_EINVAL, "lbfgs_wide_iterate: max_iter=%d < 1", max_iter);
-    Tensors T;
-    clear_tensors(T);
-    int64_t n = 0;
-    for (int i = 0; i < n_tensors; ++i) {
-        SGC_REQUIRE(numels[i] >= 0, SGC_EINVAL, "lbfgs_wide_iterate: numels[%d]=%lld < 0", i,
-                    (long long)numels[i]);
-        T.off[i] = n;
-        n += numels[i];
-        SGC_REQUIRE(n < INT32_MAX, SGC_ERANGE, "lbfgs_wide_iterate: n >= 2^31 - 1 parameters");
-    }
-    SGC_REQUIRE(n >= 1, SGC_EINVAL, "lbfgs_wide_iterate: n=0 < 1");
-    for (int i = n_tensors; i <= kMaxTensors; ++i) T.off[i] = n;
-    T.count = n_tensors;
-    Shape sh;
-    if (const int rc = find_state("lbfgs_wide_iterate", state, sh)) return rc;
-    SGC_REQUIRE(sh.n == n, SGC_EINVAL,
-                "lbfgs_wide_iterate: numels sum to %lld, the state was initialised for n=%lld",
-                (long long)n, (long long)sh.n);
-    for (int i = 0; i < n_tensors; ++i) {
-        SGC_REQUIRE(params[i] || numels[i] == 0, SGC_EINVAL,
-                    "lbfgs_wide_iterate: null parameter %d", i);
-        T.p[i] = params[i];
-        T.g[i] = grads[i];
-    }
-    SGC_REQUIRE(loss, SGC_EINVAL, "lbfgs_wide_iterate: null loss");
-    const hipError_t e = enqueue_iterate(reinterpret_cast<char *>(state), T, n, loss, (float)lr,
-                                         max_iter, max_eval, tol_grad, tol_change, s);
-    SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "lbfgs_wide_iterate launch failed: %s",
-                hipGetErrorString(e));
-    return SGC_OK;
-}
-
-int lbfgs_wide_read_status(const void *state, int64_t *out_host, hipStream_t s) {
-    SGC_REQUIRE(state, SGC_EINVAL, "lbfgs_wide_read_status: null state");
-    SGC_REQUIRE(out_host, SGC_EINVAL, "lbfgs_wide_read_status: null out_host");
-    SGC_HIP_CHECK(hipMemcpyAsync(out_host, state, 6 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    SGC_HIP_CHECK(hipStreamSynchronize(s));
-    return SGC_OK;
+    return iterate_entry<int64_t>("lbfgs_wide_iterate", kE, enqueue_iterate, state, n_tensors,
+                                  params, grads, numels, loss, lr, max_iter, max_eval, tol_grad,
+                                  tol_change, s);
 }
 
 int lbfgs_wide_sync_gram(void *state, hipStream_t s) {
     SGC_REQUIRE(state, SGC_EINVAL, "lbfgs_wide_sync_gram: null state");
-    Shape sh;
-    if (const int rc = find_state("lbfgs_wide_sync_gram", state, sh)) return rc;
+    StateShape sh;
+    if (const int rc = find_state("lbfgs_wide_sync_gram", state, kE, sh)) return rc;
     const int64_t ld = row_ld(sh.n);
     const int nv = tile_nv(ld);
     const dim3 grid((unsigned)tiles(ld));
@@ -850,8 +676,8 @@ int lbfgs_wide_sync_gram(void *state, hipStream_t s) {
 int lbfgs_wide_l2(void *state, const float *W, float *gW, int64_t numel, double l2, float *loss,
                   hipStream_t s) {
     SGC_REQUIRE(state && W && gW && loss, SGC_EINVAL, "lbfgs_wide_l2: null pointer");
-    Shape sh;
-    if (const int rc = find_state("lbfgs_wide_l2", state, sh)) return rc;
+    StateShape sh;
+    if (const int rc = find_state("lbfgs_wide_l2", state, kE, sh)) return rc;
     SGC_REQUIRE(numel >= 1 && numel <= sh.n, SGC_EINVAL,
                 "lbfgs_wide_l2: numel=%lld outside 1..n=%lld", (long long)numel, (long long)sh.n);
     if (l2 == 0.0) return SGC_OK;
@@ -861,15 +687,12 @@ int lbfgs_wide_l2(void *state, const float *W, float *gW, int64_t numel, double 
     return SGC_OK;
 }
 
-// ---- sgc_train_lbfgs_wide_f32 ----------------------------------------------------
-// train_lbfgs's loop (lbfgs.hip) on the wide iteration: per step the reset,
-// then max_iter times [xent_closure behind the state's stop word, the L2 term
-// when l2 != 0, the six launches of the iteration], then the status snapshot.
-
-// workspace: gradient [C*K + C] | loss | the fused step's workspace, each 256-B aligned
+// ---- sgc_train_lbfgs_wide_f32: run_train_steps (lbfgs_common.h) on the wide
+// iteration; the closure is xent_closure behind the state's stop word, then the
+// L2 term when l2 != 0 ----------------------------------------------------------------
 int64_t train_lbfgs_wide_workspace(int64_t M, int64_t K, int64_t C) {
     if (M <= 0 || K <= 0 || C <= 0 || C > 64 || C * K + C >= INT32_MAX) return 0;
-    return 256 + round_up((C * K + C) * 4, 256) + 256 + xent_workspace_bytes(M, K, C);
+    return train_workspace_bytes(K, C, xent_workspace_bytes(M, K, C));
 }
 
 int train_lbfgs_wide(const float *X, int64_t ldx, float *W, float *b, const int64_t *labels,
@@ -894,56 +717,20 @@ int train_lbfgs_wide(const float *X, int64_t ldx, float *W, float *b, const int6
     SGC_REQUIRE(ws_bytes >= need, SGC_ENOMEM, "%s: workspace %lld < %lld", what,
                 (long long)ws_bytes, (long long)need);
     if (steps == 0) return SGC_OK;
-    Shape sh;
-    if (const int rc = find_state(what, state, sh)) return rc;
-    SGC_REQUIRE(sh.n == n, SGC_EINVAL,
-                "%s: C*K%s = %lld parameters, the state was initialised for n=%lld", what,
-                b ? " + C" : "", (long long)n, (long long)sh.n);
-    char *p = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
-    float *grad = reinterpret_cast<float *>(p);
-    p += round_up((ck + C) * 4, 256);
-    float *loss_slot = reinterpret_cast<float *>(p);
-    p += 256;
-    void *xent_ws = p;
-    Tensors T;
-    clear_tensors(T);
-    T.count = b ? 2 : 1;
-    T.p[0] = W;
-    T.g[0] = grad;
-    T.off[0] = 0;
-    if (b) {
-        T.p[1] = b;
-        T.g[1] = grad + ck;
-        T.off[1] = ck;
-    }
-    for (int i = T.count; i <= kMaxTensors; ++i) T.off[i] = n;
     char *st = reinterpret_cast<char *>(state);
-    Header *H = reinterpret_cast<Header *>(state);
-    const int64_t *stop = &H->stop;  // (a device address: never read here)
-    const float lrf = (float)lr;
-    for (int32_t step = 0; step < steps; ++step) {
-        hipLaunchKernelGGL(wide_begin_kernel, dim3(1), dim3(1), 0, s, H);
-        SGC_HIP_CHECK(hipGetLastError());
-        for (int32_t it = 0; it < max_iter; ++it) {
-            float *loss = (it == 0 && loss_trace) ? loss_trace + step : loss_slot;
-            if (const int rc = xent_closure(stop, X, ldx, W, b, labels, M, K, C, loss, grad,
-                                            b ? grad + ck : nullptr, xent_ws, s))
-                return rc;
-            hipError_t e = hipSuccess;
-            if (l2 != 0.0) e = enqueue_l2(st, sh, W, grad, ck, l2, loss, s);
-            if (e == hipSuccess)
-                e = enqueue_iterate(st, T, n, loss, lrf, max_iter, max_eval, tol_grad, tol_change,
-                                    s);
-            SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "%s launch failed: %s", what,
-                        hipGetErrorString(e));
-        }
-        if (status_trace) {
-            hipLaunchKernelGGL(wide_snapshot_kernel, dim3(1), dim3(1), 0, s, H,
-                               status_trace + 6 * (int64_t)step);
-            SGC_HIP_CHECK(hipGetLastError());
-        }
-    }
-    return SGC_OK;
+    auto closure = [&](const StateShape &sh, const int64_t *stop, float *loss, float *dW,
+                       float *db, void *xent_ws) -> int {
+        if (const int rc =
+                xent_closure(stop, X, ldx, W, b, labels, M, K, C, loss, dW, db, xent_ws, s))
+            return rc;
+        if (l2 == 0.0) return SGC_OK;
+        const hipError_t e = enqueue_l2(st, sh, W, dW, ck, l2, loss, s);
+        SGC_REQUIRE(e == hipSuccess, SGC_EHIP, "%s launch failed: %s", what, hipGetErrorString(e));
+        return SGC_OK;
+    };
+    return run_train_steps<int64_t>(what, kE, closure, enqueue_iterate, W, b, K, C, state, steps,
+                                    lr, max_iter, max_eval, tol_grad, tol_change, loss_trace,
+                                    status_trace, ws, s);
 }
 
 SGC_WARM_UNIT(warm_lbfgs_wide)

@@ -59,6 +59,7 @@ the device path and torch's own step() can alternate on one optimiser.
 step() is one sgc_adam_step_f32 launch per param group; run_epochs() is the
 whole training loop in one host call (sgc_train_adam_f32).  See the class.
 """
+import collections
 import ctypes
 import weakref
 
@@ -78,13 +79,32 @@ STOP_NONE, STOP_OPT_AT_ENTRY, STOP_MAX_ITER, STOP_MAX_EVAL, STOP_OPT, STOP_GTD, 
     STOP_STEP_SMALL, STOP_LOSS_CHANGE = range(8)
 
 
-def _read_status(lib, state, stream, wide=False):
+# The calls of one engine (narrow: csrc/lbfgs.hip, wide: csrc/lbfgs_wide.hip),
+# chosen once per optimiser, when its device state is built.
+_Engine = collections.namedtuple("_Engine", "workspace init begin_step iterate read_status wide")
+
+
+def _engine(lib, wide):
+    w = "wide_" if wide else ""
+    return _Engine(*[getattr(lib, f"sgc_lbfgs_{w}{name}") for name in
+                     ("workspace", "init", "begin_step", "iterate_f32", "read_status")], bool(wide))
+
+
+def _read_status(engine, state, stream):
     """(n_iter, func_evals, iters, evals, stop, hist_len): the one host
     synchronisation of a step."""
     out = (ctypes.c_int64 * 6)()
-    read = lib.sgc_lbfgs_wide_read_status if wide else lib.sgc_lbfgs_read_status
-    _lib.check(read(_lib.ptr(state), out, stream), "lbfgs_read_status")
+    _lib.check(engine.read_status(_lib.ptr(state), out, stream), "lbfgs_read_status")
     return tuple(out)
+
+
+def _grow_ws(owner, nbytes, dev):
+    """owner._train_ws, the workspace of the owner's fused calls: kept between
+    calls, replaced when too small or on another device."""
+    ws = getattr(owner, "_train_ws", None)
+    if ws is None or ws.numel() < nbytes or ws.device != dev:
+        ws = owner._train_ws = torch.empty(max(1, nbytes), dtype=torch.uint8, device=dev)
+    return ws
 
 
 def _read_status_trace(table):
@@ -114,6 +134,7 @@ class LBFGS(torch.optim.LBFGS, metaclass=_WideOption):
         self.poll_every = None if poll_every is None else int(poll_every)
         self.wide = False       # LBFGS(..., wide=True): see the module docstring
         self._dev_wide = False  # the device state is sgc_lbfgs_wide_workspace's
+        self._engine = None     # the _Engine that built the device state
         self._dev_state = None  # uint8 device tensor (sgc_lbfgs_workspace bytes)
         self._dev_key = None    # (parameter identities and shapes, history_size) it was built for
         self.last_status = None  # (n_iter, func_evals, iters, evals, stop, hist_len) of the last step
@@ -157,15 +178,12 @@ class LBFGS(torch.optim.LBFGS, metaclass=_WideOption):
             wide = self._dev_wide if self._dev_state is not None else \
                 sum(p.numel() for p in ps) > MAX_NUMEL
             state = self._ensure_state(lib, dev, stream, wide)
-            begin_step = lib.sgc_lbfgs_wide_begin_step if wide else lib.sgc_lbfgs_begin_step
-            iterate = lib.sgc_lbfgs_wide_iterate_f32 if wide else lib.sgc_lbfgs_iterate_f32
-            read = (lambda: _read_status(lib, state, stream, True)) if wide else \
-                (lambda: _read_status(lib, state, stream))
+            eng = self._engine
             nt = len(ps)
             p_ptrs = (ctypes.c_void_p * nt)(*[p.data_ptr() for p in ps])
             numels = (ctypes.c_int64 * nt)(*[p.numel() for p in ps])
             lr = float(group["lr"])
-            _lib.check(begin_step(_lib.ptr(state), stream), "lbfgs_begin_step")
+            _lib.check(eng.begin_step(_lib.ptr(state), stream), "lbfgs_begin_step")
             orig_loss = None
             status = None
             for it in range(group["max_iter"]):
@@ -176,18 +194,18 @@ class LBFGS(torch.optim.LBFGS, metaclass=_WideOption):
                 grads = [self._dense_grad(p) for p in ps]  # kept alive until the launch is queued
                 g_ptrs = (ctypes.c_void_p * nt)(*[None if g is None else g.data_ptr()
                                                   for g in grads])
-                _lib.check(iterate(
+                _lib.check(eng.iterate(
                     _lib.ptr(state), nt, p_ptrs, g_ptrs, numels, _lib.ptr(dloss), lr,
                     group["max_iter"], group["max_eval"], float(group["tolerance_grad"]),
                     float(group["tolerance_change"]), stream), "lbfgs_iterate_f32")
                 if self.poll_every and (it + 1) % self.poll_every == 0 and \
                         it + 1 < group["max_iter"]:
-                    status = read()
+                    status = _read_status(eng, state, stream)
                     if status[4] != STOP_NONE:
                         break
                     status = None
             if status is None:
-                status = read()
+                status = _read_status(eng, state, stream)
         self.last_status = status
         st = self.state[ps[0]]
         st["n_iter"], st["func_evals"] = int(status[0]), int(status[1])
@@ -199,15 +217,15 @@ class LBFGS(torch.optim.LBFGS, metaclass=_WideOption):
         if self._dev_state is None:
             group = self.param_groups[0]
             n = sum(p.numel() for p in self._params)
-            workspace = lib.sgc_lbfgs_wide_workspace if wide else lib.sgc_lbfgs_workspace
-            init = lib.sgc_lbfgs_wide_init if wide else lib.sgc_lbfgs_init
-            nbytes = workspace(n, group["history_size"])
+            eng = _engine(lib, wide)
+            nbytes = eng.workspace(n, group["history_size"])
             if nbytes <= 0:
                 _lib.check(1, "lbfgs_workspace")
             state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _lib.check(init(_lib.ptr(state), nbytes, n, group["history_size"], stream),
+            _lib.check(eng.init(_lib.ptr(state), nbytes, n, group["history_size"], stream),
                        "lbfgs_init")
-            self._dev_state, self._dev_key, self._dev_wide = state, self._key(), bool(wide)
+            self._dev_state, self._dev_key, self._dev_wide = state, self._key(), eng.wide
+            self._engine = eng
         elif self._dev_wide != bool(wide):
             raise ValueError("sgc_amd.optim.LBFGS: the device state was built by the %s kernel; "
                              "one optimiser cannot alternate between the two" %
@@ -258,11 +276,13 @@ class LBFGS(torch.optim.LBFGS, metaclass=_WideOption):
             return None
         return W, b, x
 
-    def _run_steps_wide(self, plan, labels, steps, l2):
-        """run_steps' fused path on sgc_train_lbfgs_wide_f32; None (no device
-        state built, no launch) when the shape is past
-        the fused closure's 31-bit offset limits, which the call reports as
-        SGC_ERANGE from its argument checks: the literal loop runs then."""
+    def _run_fused(self, plan, labels, steps, l2, wide):
+        """run_steps' fused path: one sgc_train_lbfgs_f32 / _x16 call, or with
+        `wide` one sgc_train_lbfgs_wide_f32 call (the only one that takes l2),
+        and one read-back of the status table.  None (no device state built,
+        no launch) when the wide call's shape is past the fused closure's
+        31-bit offset limits, which it reports as SGC_ERANGE from its argument
+        checks: the literal loop runs then."""
         if self._dev_state is not None and self._key() != self._dev_key:
             raise ValueError("sgc_amd.optim.LBFGS: the parameter list or history_size changed "
                              "after the first step")
@@ -274,28 +294,32 @@ class LBFGS(torch.optim.LBFGS, metaclass=_WideOption):
         C = W.shape[0]
         dev = x.device
         lib = _lib.load()
-        ws_bytes = lib.sgc_train_lbfgs_wide_workspace(M, K, C)
-        ws = getattr(self, "_train_ws", None)
-        if ws is None or ws.numel() < ws_bytes or ws.device != dev:
-            ws = self._train_ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=dev)
+        kind = "wide_f32" if wide else "x16" if is_x16(x) else "f32"
+        train = getattr(lib, "sgc_train_lbfgs_" + kind)
+        ws_bytes = getattr(lib, {"wide_f32": "sgc_train_lbfgs_wide_workspace",
+                                 "x16": "sgc_train_lbfgs_x16_workspace",
+                                 "f32": "sgc_train_lbfgs_workspace"}[kind])(M, K, C)
+        ws = _grow_ws(self, ws_bytes, dev)
         losses = torch.empty(steps, dtype=torch.float32, device=dev)
         table = torch.empty(steps * 6, dtype=torch.int64, device=dev)
+        head = (_lib.ptr(x), X16_DTYPES[x.dtype], x.stride(0)) if kind == "x16" else \
+            (_lib.ptr(x), x.stride(0))
+        tols = (float(group["tolerance_grad"]), float(group["tolerance_change"])) + \
+            ((l2,) if wide else ())
         with torch.no_grad(), torch.cuda.device(dev):
             stream = _lib.stream_handle(dev)
 
             def call(state, n_steps):
-                return lib.sgc_train_lbfgs_wide_f32(
-                    _lib.ptr(x), x.stride(0), _lib.ptr(W), None if b is None else _lib.ptr(b),
-                    _lib.ptr(y), M, K, C, _lib.ptr(state), n_steps, float(group["lr"]),
-                    group["max_iter"], group["max_eval"], float(group["tolerance_grad"]),
-                    float(group["tolerance_change"]), float(l2), _lib.ptr(losses),
-                    _lib.ptr(table), _lib.ptr(ws), ws.numel(), stream)
+                return train(*head, _lib.ptr(W), None if b is None else _lib.ptr(b), _lib.ptr(y),
+                             M, K, C, _lib.ptr(state), n_steps, float(group["lr"]),
+                             group["max_iter"], group["max_eval"], *tols, _lib.ptr(losses),
+                             _lib.ptr(table), _lib.ptr(ws), ws.numel(), stream)
             # the argument checks alone (steps = 0 returns after them, before
             # the state is looked at): a shape the closure refuses has no plan
-            if ws_bytes <= 0 or call(ws, 0) == _SGC_ERANGE:
+            if wide and (ws_bytes <= 0 or call(ws, 0) == _SGC_ERANGE):
                 return None
-            state = self._ensure_state(lib, dev, stream, True)
-            _lib.check(call(state, steps), "train_lbfgs_wide_f32")
+            _lib.check(call(self._ensure_state(lib, dev, stream, wide), steps),
+                       "train_lbfgs_" + kind)
             self.step_statuses = _read_status_trace(table)
         self.last_status = self.step_statuses[-1]
         st = self.state[self._params[0]]
@@ -341,7 +365,7 @@ class LBFGS(torch.optim.LBFGS, metaclass=_WideOption):
             wide_plan = self._fused_plan(model, features, labels, wide=True)
             if wide_plan is not None:
                 model.train()
-                losses = self._run_steps_wide(wide_plan, labels, steps, l2)
+                losses = self._run_fused(wide_plan, labels, steps, l2, True)
                 if losses is not None:
                     return losses
         model.train()
@@ -360,43 +384,7 @@ class LBFGS(torch.optim.LBFGS, metaclass=_WideOption):
                 losses.append(torch.as_tensor(loss).detach())
                 self.step_statuses.append(self.last_status)
             return torch.stack(losses)
-        if self._dev_state is not None and self._key() != self._dev_key:
-            raise ValueError("sgc_amd.optim.LBFGS: the parameter list or history_size changed "
-                             "after the first step")
-        W, b, x = plan
-        self.zero_grad(set_to_none=True)
-        group = self.param_groups[0]
-        y = labels.contiguous()
-        M, K = x.shape
-        C = W.shape[0]
-        dev = x.device
-        lib = _lib.load()
-        x16 = is_x16(x)
-        ws_bytes = (lib.sgc_train_lbfgs_x16_workspace if x16 else
-                    lib.sgc_train_lbfgs_workspace)(M, K, C)
-        ws = getattr(self, "_train_ws", None)
-        if ws is None or ws.numel() < ws_bytes or ws.device != dev:
-            ws = self._train_ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=dev)
-        losses = torch.empty(steps, dtype=torch.float32, device=dev)
-        table = torch.empty(steps * 6, dtype=torch.int64, device=dev)
-        with torch.no_grad(), torch.cuda.device(dev):
-            stream = _lib.stream_handle(dev)
-            state = self._ensure_state(lib, dev, stream)
-            tail = (_lib.ptr(W), _lib.ptr(b), _lib.ptr(y), M, K, C, _lib.ptr(state), steps,
-                    float(group["lr"]), group["max_iter"], group["max_eval"],
-                    float(group["tolerance_grad"]), float(group["tolerance_change"]),
-                    _lib.ptr(losses), _lib.ptr(table), _lib.ptr(ws), ws.numel(), stream)
-            if x16:
-                _lib.check(lib.sgc_train_lbfgs_x16(_lib.ptr(x), X16_DTYPES[x.dtype], x.stride(0),
-                                                   *tail), "train_lbfgs_x16")
-            else:
-                _lib.check(lib.sgc_train_lbfgs_f32(_lib.ptr(x), x.stride(0), *tail),
-                           "train_lbfgs_f32")
-            self.step_statuses = _read_status_trace(table)
-        self.last_status = self.step_statuses[-1]
-        st = self.state[self._params[0]]
-        st["n_iter"], st["func_evals"] = int(self.last_status[0]), int(self.last_status[1])
-        return losses
+        return self._run_fused(plan, labels, steps, l2, False)
 
     @staticmethod
     def _device_loss(loss, dev):
@@ -676,9 +664,7 @@ class Adam(torch.optim.Adam):
         x16 = is_x16(x)
         ws_bytes = (lib.sgc_train_adam_x16_workspace if x16 else
                     lib.sgc_train_adam_workspace)(M, K, C)
-        ws = getattr(self, "_train_ws", None)
-        if ws is None or ws.numel() < ws_bytes or ws.device != dev:
-            ws = self._train_ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=dev)
+        ws = _grow_ws(self, ws_bytes, dev)
         trace = torch.empty(epochs, dtype=torch.float32, device=dev)
         b1, b2 = group["betas"]
         with torch.no_grad(), torch.cuda.device(dev):

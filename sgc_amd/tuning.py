@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from .metrics import Evaluation
 from .models import SGC, _check_eval_labels
-from .optim import Adam, _labels_have_ignored
+from .optim import Adam, _grow_ws, _labels_have_ignored
 
 MAX_MODELS = 4096
 
@@ -261,9 +261,7 @@ class AdamSweep:
             self._wd_dev = torch.tensor(self.weight_decays, dtype=torch.float32).to(dev)
         lib = _lib.load()
         ws_bytes = lib.sgc_train_adam_sweep_workspace(B, M, K, C)
-        ws = self._train_ws
-        if ws is None or ws.numel() < ws_bytes or ws.device != dev:
-            ws = self._train_ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=dev)
+        ws = _grow_ws(self, ws_bytes, dev)
         trace = torch.empty((B, epochs), dtype=torch.float32, device=dev)
         b1, b2 = group["betas"]
         for m, opt in zip(bank.models, self.optimizers):

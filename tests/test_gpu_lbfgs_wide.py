@@ -309,6 +309,40 @@ def test_numels_must_sum_to_the_states_n(lib):
     torch.cuda.synchronize()
 
 
+def test_either_init_replaces_the_registry_entry(lib):
+    """One address initialised by one engine, then by the other: the registry
+    keeps the last init only, so the first engine's calls are refused at their
+    argument checks (nothing is launched) and the second engine's run."""
+    from sgc_amd import _lib
+    n, hs = 40, 3
+    nbytes = lib.sgc_lbfgs_wide_workspace(n, hs)
+    assert nbytes >= lib.sgc_lbfgs_workspace(n, hs) > 0
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    assert buf.data_ptr() % 256 == 0
+    stream = _lib.stream_handle(DEV)
+    p = torch.ones(n, device=DEV)
+    g = torch.full((n,), 0.5, device=DEV)
+    loss = torch.ones(1, device=DEV)
+    args = (_lib.ptr(buf), 1, (ctypes.c_void_p * 1)(p.data_ptr()),
+            (ctypes.c_void_p * 1)(g.data_ptr()), (ctypes.c_int64 * 1)(n), _lib.ptr(loss), 1.0, 20,
+            25, 1e-7, 1e-9, stream)
+
+    def refused(rc, init):
+        return rc == 1 and b"not initialised by " + init in lib.sgc_last_error()
+    _lib.check(lib.sgc_lbfgs_init(_lib.ptr(buf), nbytes, n, hs, stream), "init")
+    _lib.check(lib.sgc_lbfgs_wide_init(_lib.ptr(buf), nbytes, n, hs, stream), "wide_init")
+    assert refused(lib.sgc_lbfgs_iterate_f32(*args), b"sgc_lbfgs_init")
+    assert lib.sgc_lbfgs_wide_iterate_f32(*args) == 0
+    _lib.check(lib.sgc_lbfgs_init(_lib.ptr(buf), nbytes, n, hs, stream), "init")
+    assert refused(lib.sgc_lbfgs_wide_iterate_f32(*args), b"sgc_lbfgs_wide_init")
+    assert refused(lib.sgc_lbfgs_wide_sync_gram(_lib.ptr(buf), stream), b"sgc_lbfgs_wide_init")
+    assert refused(lib.sgc_lbfgs_wide_l2_f32(_lib.ptr(buf), _lib.ptr(p), _lib.ptr(g), n, 1e-3,
+                                             _lib.ptr(loss), stream), b"sgc_lbfgs_wide_init")
+    assert lib.sgc_lbfgs_iterate_f32(*args) == 0
+    torch.cuda.synchronize()
+    assert torch.isfinite(p).all()
+
+
 # --- the Gram block ---------------------------------------------------------------------
 
 @pytest.mark.parametrize("name", ["reject_full_ring", "full_ring", "two_steps"])
